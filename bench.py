@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: cells/sec through one MMVAE training step (BASELINE.json metric), on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds the figures that take runs of their
+own behind the timed region (`roofline`, `parity`, `cpu_baseline`, `data_parallel`).  --dump-outputs DIR writes what the
+last timed step computed (dump_outputs below); the inputs are seeded, so two builds can be compared output for output.
 
 A step = zero_grad, forward, ELBO, [adversarial D/G phases], backward, global-norm clip, Adam for the shared VAE and
 the active expert, on a synthetic batch that is already resident in HBM.  Modalities alternate round-robin on a fixed,
@@ -56,6 +60,11 @@ def parse():
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: rehearsal of the launch / exchange / timing logic on the gloo backend with CPU plumbing "
                          "(module path, plain torch ops; tests/test_bench_entry.py) -- never a measurement")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need, behind the "
+                    "timed region: the roofline leg, the parity block, the CPU baseline and (N > 1) the same loop without "
+                    "the gradient exchange")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed as "
+                    "DIR/<name>.npy (float32 / float64, at most 64 MB; larger tensors as a fixed seeded sample)")
     return ap.parse_args()
 
 
@@ -264,6 +273,63 @@ def cpu_baseline(cfg, seconds):
                       f"CPU fp32; sweep " + ", ".join(f"{t} threads: {sweep[t][0]:.0f} cells/s" for t in counts)}
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 1 << 16  # entries kept of a larger tensor (at most; fewer when the budget needs it)
+
+
+def dump_outputs(dirname, model, result, write=True):
+    """--dump-outputs: what the last timed step computed, as its caller receives it, one DIR/<name>.npy per array.
+    A training step returns nothing: its outputs are the model's log after it (`logged.<name>`: losses, gradient norms,
+    the latest value of every logged name) and the model's state (`state.<name>`: parameters and BatchNorm statistics).
+    validation / predict steps: the tensors they return (`result.<name>`: loss terms / latent embeddings).  Floating
+    tensors stay float32 (float64 if they are), anything else becomes float64; a tensor over DUMP_SAMPLE entries is
+    written as its flattened entries at sorted indices drawn without replacement by numpy.random.default_rng(crc32 of
+    its name) -- the same indices in every run.  Called on every rank (state_dict() flushes the engine); only `write`
+    ranks write."""
+    import re
+    import zlib
+
+    import numpy as np
+
+    arrays = {}
+
+    def add(name, v):
+        if torch.is_tensor(v):
+            arrays[name] = v.detach()
+        elif isinstance(v, (int, float, bool)):
+            arrays[name] = torch.tensor(float(v), dtype=torch.float64)
+        elif isinstance(v, dict):
+            for k, x in v.items():
+                add(f"{name}.{k}", x)
+        elif isinstance(v, (tuple, list)):
+            for k, x in enumerate(v):
+                add(f"{name}.{k}", x)
+        # (anything else -- the metadata frame a predict step echoes back -- is an input, not a result)
+
+    if result is None:  # training step
+        for k, v in model.logged.items():
+            add(f"logged.{k}", v)
+        for k, v in model.state_dict().items():
+            add(f"state.{k}", v)
+    else:
+        add("result", result)
+    cap = DUMP_SAMPLE
+    while sum(min(t.numel(), cap) * 8 for t in arrays.values()) > DUMP_BYTES and cap > 1:
+        cap //= 2
+    if not write:
+        return
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        fname = re.sub(r"[^A-Za-z0-9_.-]", "_", name)
+        flat = t.reshape(-1)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(flat.numel(), cap, replace=False))
+            t = flat[torch.from_numpy(idx).to(flat.device)]
+        keep = t.dtype if t.dtype in (torch.float32, torch.float64) else (
+            torch.float32 if t.is_floating_point() else torch.float64)
+        np.save(os.path.join(dirname, f"{fname}.npy"), t.to(keep).cpu().numpy())
+
+
 def build_model(a, cfg, device):
     """The benchmark's model: configs/model/<config>.yaml through the class_path / init_args instantiator (the drop-in
     surface), or -- `--genes` diagnostics -- the same architecture from mmvae_amd.synthetic with other gene counts."""
@@ -407,11 +473,10 @@ def main():
                 # that step's first forward product beside this step's forward chain.  Every timed step still runs
                 # exactly one such product -- the next step's instead of its own.
                 model.hint_next_batch(batch_of(i + 1))
-            model.training_step((x, meta, eid), i)
-        elif a.mode == "validate":
-            model.validation_step((x, meta, eid))
-        else:
-            model.predict_step((x, meta, eid), i)
+            return model.training_step((x, meta, eid), i)
+        if a.mode == "validate":
+            return model.validation_step((x, meta, eid))
+        return model.predict_step((x, meta, eid), i)
 
     def sync():
         if on_gpu:
@@ -466,8 +531,9 @@ def main():
     t0 = time.perf_counter()
     if marks:
         marks[0].record()
+    last = None
     for i in range(a.steps):
-        step(n_setup + a.warmup + i)
+        last = step(n_setup + a.warmup + i)
         if marks:
             marks[i + 1].record()
     if prof is not None:
@@ -490,17 +556,19 @@ def main():
             print(f"{(t - t_first) / 100.0:9.1f} us  {name}", file=sys.stderr)
     if feed is not None:
         feed.close()  # stops the feed's background threads before the interpreter shuts down
+    if a.dump_outputs:  # before anything else runs on the model
+        dump_outputs(a.dump_outputs, model, last, write=rank == 0)
     if world > 1:
         t = torch.tensor([el], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         el = float(t)
     leg = None
-    if on_gpu and a.mode == "train" and feed is None and getattr(model, "_engine", None) and not a.no_engine:
+    if a.full and on_gpu and a.mode == "train" and feed is None and getattr(model, "_engine", None) and not a.no_engine:
         leg = time_step_kernels(model, step, n_setup + a.warmup + a.steps)  # every rank: the steps exchange gradients
     # N > 1: the same loop once more with the gradient all-reduces skipped (mmvae_amd.dist.DRY_RUN) -- what the step
     # costs without the transfers; `ms_per_step` minus this is the exchange the overlapped program did NOT hide
     dp_diag = None
-    if world > 1 and a.mode == "train" and feed is None:
+    if a.full and world > 1 and a.mode == "train" and feed is None:
         n_dry = max(min(a.steps, 20), 2 * len(eids))
         base = n_setup + a.warmup + a.steps + 16
         mdist.DRY_RUN = True
@@ -659,7 +727,7 @@ def main():
         if dp_diag is not None:
             dp_diag["ms_exposed_exchange"] = el / a.steps * 1e3 - dp_diag["ms_per_step_without_transfers"]
             out["data_parallel"] = dp_diag
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, a.cpu_seconds)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())

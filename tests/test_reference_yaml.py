@@ -80,18 +80,27 @@ def _build_reference_module(node):
         instantiate.ALIASES = aliases
 
 
+# The reference's model YAMLs by name: the same cases are collected whether a checkout of it is at hand or not
+# (test_the_reference_ships_model_yamls holds the list to the checkout).
+MODEL_YAMLS = ["configs/model/compare/adversarial-conditional.yaml", "configs/model/compare/adversarial.yaml",
+               "configs/model/compare/conditional.yaml", "configs/model/compare/plain_vae.yaml",
+               "configs/model/config.yaml", "configs/model/configV2.yaml", "configs/model/configV3.yaml",
+               "configs/model/human_only.yaml", "configs/model/parallel/adversarial-conditional.yaml",
+               "configs/model/parallel/conditional.yaml"]
+
+
 def _model_yamls():
     return sorted(glob.glob(os.path.join(REF, "configs", "model", "**", "*.yaml"), recursive=True))
 
 
 def test_the_reference_ships_model_yamls():
     assert any(p.endswith("human_only.yaml") for p in _model_yamls())
+    assert [os.path.relpath(p, REF) for p in _model_yamls()] == MODEL_YAMLS
 
 
-@pytest.mark.parametrize("path", _model_yamls() or ["<none>"], ids=lambda p: os.path.relpath(p, REF) if p != "<none>" else p)
+@pytest.mark.parametrize("path", MODEL_YAMLS, ids=str)
 def test_reference_model_yaml_loads_unchanged_with_the_same_checkpoint_keys(path, tmp_path):
-    if path == "<none>":
-        pytest.skip("no model YAML found")
+    path = os.path.join(REF, path)
     from mmvae_amd import backend, instantiate
     from mmvae_amd.modules import base
 

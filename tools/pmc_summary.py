@@ -1,12 +1,14 @@
 """Summarise the separate rocprofv3 --pmc passes of tools/roofline_kernel.py collected by tools/collect_profiles.sh:
 per counter the value per launch of the roofline kernel (the GEMM with the most launches in the pass).
-usage: python tools/pmc_summary.py TAG  (reads gpurun_out/pmc_TAG_<counter>/…/p_counter_collection.csv)"""
+usage: python tools/pmc_summary.py TAG [DIR]  (reads DIR/pmc_TAG_<counter>/…/p_counter_collection.csv; DIR defaults to
+profile_out, the output directory of tools/collect_profiles.sh)"""
 import csv
 import glob
 import sys
 from collections import defaultdict
 
 tag = sys.argv[1]
+out = sys.argv[2] if len(sys.argv) > 2 else "profile_out"
 print("pass,kernel,counter,launches,value_per_launch,note")
 notes = {
     "FETCH_SIZE": "KiB; gfx950 tallies 128-B read requests at 64 B: x2 for 16-B/lane streaming reads",
@@ -17,7 +19,7 @@ notes = {
     "SQ_INSTS_LDS": "LDS instructions (wave-level) of the launch",
     "SQ_INSTS_VMEM_RD": "vector memory read instructions (wave-level) of the launch",
 }
-for d in sorted(glob.glob(f"gpurun_out/pmc_{tag}_*")):
+for d in sorted(glob.glob(f"{out}/pmc_{tag}_*")):
     files = glob.glob(d + "/**/*counter_collection.csv", recursive=True)
     if not files:
         continue
