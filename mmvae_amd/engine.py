@@ -55,9 +55,7 @@ class EngineSettings:
     side_dw_dp: int = 125        # MMVAE_SIDE_DW_DP: that branch inside the exchange (data-parallel) program; 0 = in order
     side_dw_any: bool = False    # MMVAE_SIDE_DW_ANY=1: fork outside the measured geometry too
     prefetch_adv: int = 86       # MMVAE_PREFETCH_ADV: its cap in adversarial programs (second branch stream, beside the adversaries' lane: 3 rounds of the 256 work items; C4 1.091 -> 1.070 ms, 128: 1.083, 64: 1.094); 0 = off
-    prefetch_join: bool = False  # MMVAE_PREFETCH_JOIN=1: join that product ahead of the reconstruction launch (diagnostics)
     cond_batched: bool = True    # MMVAE_COND_BATCHED=0: conditional layers of a "parallel" selection order one launch per position
-    x_planes: bool = False       # MMVAE_X_PLANES=1: the batch pre-split for the first layer's weight gradient even where that GEMM can read it as fp32 (see StepEngine._x_planes)
     prefetch: int = 128          # MMVAE_PREFETCH: workgroup cap of the NEXT step's first forward GEMM beside this step's forward chain (software pipelining across steps, needs the caller's hint); 0 = off
     adv_fused: bool = True       # MMVAE_ADV_FUSED=0: the per-layer adversary program (the path of adversaries with BatchNorm)
     adv_aside: int = 2           # MMVAE_ADV_ASIDE: 0 the fused adversary passes in order; 1 on the branch stream; 2 + the decoder's weight gradient on a second branch from where the first is joined
@@ -79,8 +77,8 @@ class EngineSettings:
             conditionals=e("MMVAE_ENGINE_CONDITIONALS", "1") != "0", graphs=e("MMVAE_NO_GRAPH", "0") == "0",
             planes=e("MMVAE_PLANES", "1") != "0", side_dw=int(e("MMVAE_SIDE_DW", "125")),
             side_dw2=int(e("MMVAE_SIDE_DW2", "185")), side_dw_dp=int(e("MMVAE_SIDE_DW_DP", "125")),
-            side_dw_any=e("MMVAE_SIDE_DW_ANY", "0") != "0", prefetch=int(e("MMVAE_PREFETCH", "128")), prefetch_join=e("MMVAE_PREFETCH_JOIN", "0") == "1",
-            cond_batched=e("MMVAE_COND_BATCHED", "1") != "0", x_planes=e("MMVAE_X_PLANES", "0") == "1", prefetch_adv=int(e("MMVAE_PREFETCH_ADV", "86")),
+            side_dw_any=e("MMVAE_SIDE_DW_ANY", "0") != "0", prefetch=int(e("MMVAE_PREFETCH", "128")),
+            cond_batched=e("MMVAE_COND_BATCHED", "1") != "0", prefetch_adv=int(e("MMVAE_PREFETCH_ADV", "86")),
             adv_fused=e("MMVAE_ADV_FUSED", "1") != "0",
             adv_aside=int(e("MMVAE_ADV_ASIDE", "2")),
             dp_overlap=None if ov == "" else ov != "0", dp_shard=e("MMVAE_DP_SHARD", "1") != "0", dp_kernels=kernels,
@@ -132,6 +130,62 @@ def forks_allowed(settings: "EngineSettings", runtime: Optional[str] = None) -> 
     """May captured programs fork onto branch streams on this HIP runtime?"""
     v = (torch.version.hip or "") if runtime is None else runtime
     return bool(settings.side_dw_any) or any(v.startswith(p) for p in FORK_VALIDATED_RUNTIMES)
+
+
+@dataclass(frozen=True)
+class _Layout:
+    """Where a plan's launches run: every branch stream decision of the program, made once per plan (plan_layout).  A cap
+    is the workgroup count of a persistent GEMM grid on a branch (the chain beside it gets the remaining CUs); 0 = no
+    such branch."""
+    big: bool            # the G-wide weight gradient is >= 5 GFLOP
+    side_dw: int         # the decoder's weight gradient on the side branch (in-order single-rank program)
+    early: bool          # the loss words behind it on that branch
+    late: bool           # the VAE optimiser on the branch beside the encoder's weight gradient, capped to late_cap
+    late_cap: int
+    adv_aside: bool      # the fused adversaries' passes on the branch stream (when their program builds)
+    adv_dw2: bool        # + the decoder's weight gradient on the second branch, capped to ADV_DW_CAP
+    adv_lane: bool       # the adversaries' section as a lane of its own under a gradient exchange
+    dp_dw: int           # the decoder's weight gradient on the side branch of the exchange program
+    prefetch: bool       # the next step's first forward product beside this step's forward chain ...
+    prefetch_cap: int    # ... capped to this,
+    prefetch_side2: bool  # ... on the second branch stream (adversarial programs) instead of the side stream
+
+
+def plan_layout(st: EngineSettings, *, fork_ok: bool, side_stream: bool, side_stream2: bool, lane_stream: bool,
+                overlap: bool, world: int, mode: str, B: int, K: int, R: int, G: int, n_in_last: int, iwae: bool,
+                has_adv: bool, has_cond: bool, adv_reducer: bool) -> _Layout:
+    """The branch layout of a plan from the settings, the engine's facts (validated runtime, branch streams, exchange,
+    world size) and the plan's geometry; no library queries.  The caps are tuned for the shape where the two weight
+    gradients are SHORTER than the chains they hide behind (C2: B = 512, K = 1: 105 us of GEMM beside a 190 us chain);
+    with K samples or bigger batches a capped GEMM becomes the critical path (C3 4.36 against 4.00 ms, C5 7.03 against
+    5.93 ms, C4 1.64 against 1.60 ms with the branches on).  The forked program is the default only for the geometry its
+    caps were measured on (a G-wide weight gradient of ~21 GFLOP +-25 %, <= 640 rows), where it has run > 10^4 replays
+    without a fault: small models and other shapes stay on ONE stream unless MMVAE_SIDE_DW_ANY=1 asks for it (the
+    hipGraphLaunch hazard of the toy shapes has no root cause yet: DESIGN.md section 5)."""
+    train = mode == "train"
+    dw_flops = 2.0 * G * n_in_last * R
+    big = dw_flops >= 5e9
+    measured = big and (0.75 * 2.1e10 <= dw_flops <= 1.25 * 2.1e10 or st.side_dw_any)  # (or asked for anywhere)
+    in_order = not overlap and world == 1 and K == 1  # single-rank in-order program, one sample
+    side_dw = st.side_dw if fork_ok else 0  # (StepEngine.side_dw)
+    side_dw = side_dw if (train and side_stream and in_order and R <= SIDE_MAX_ROWS and not has_adv and measured) else 0
+    # the late branch alone also serves the adversarial programs: their branch stream is free again once the adversaries'
+    # passes have been joined
+    late = bool(side_dw or (st.side_dw2 and side_stream and train and has_adv and in_order and R <= SIDE_MAX_ROWS
+                            and measured and st.adv_aside))
+    adv_fused = has_adv and train and st.adv_fused
+    adv_dp = overlap or adv_reducer
+    adv_aside = bool(adv_fused and not adv_dp and st.adv_aside and side_stream and in_order and measured and not has_cond)
+    adv_forks = bool(adv_fused and st.adv_aside >= 2 and side_stream2 and in_order and measured and not has_cond
+                     and not adv_reducer)
+    dp_dw = st.side_dw_dp if fork_ok else 0  # (StepEngine.side_dw_dp)
+    dp_dw = dp_dw if (overlap and side_stream and train and K == 1 and not has_adv and measured and not has_cond) else 0
+    return _Layout(
+        big=big, side_dw=side_dw, early=bool(side_dw and not iwae), late=late, late_cap=st.side_dw2,
+        adv_aside=adv_aside, adv_dw2=bool(adv_aside and side_stream2 and st.adv_aside >= 2),
+        adv_lane=bool(adv_fused and adv_dp and st.adv_aside and lane_stream and K == 1 and not has_cond), dp_dw=dp_dw,
+        prefetch=bool(train and (side_dw or adv_forks)),
+        prefetch_cap=st.prefetch_adv if adv_forks else st.prefetch, prefetch_side2=adv_forks)
 
 
 class StepEngine:
@@ -211,22 +265,22 @@ class StepEngine:
             warnings.warn(f"mmvae_amd.engine: HIP runtime {torch.version.hip} is not one the forked step programs were "
                           f"validated on {FORK_VALIDATED_RUNTIMES}: single-stream programs (MMVAE_SIDE_DW_ANY=1 overrides)")
             self.side_dw = 0
-        # cap of the expert encoder's weight gradient while the shared VAE's optimiser (and the loss words, the bias
-        # column sums) run beside it on the branch stream (553 items at C2: 3 rounds on 185 workgroups as on 256)
-        self.side_dw2 = st.side_dw2
         # the decoder's branch inside the exchange program (data parallelism): beside the part of the backward chain that
         # lies ahead of the shared VAE's exchange point (the cut joins it); 0 = in order
         self.side_dw_dp = st.side_dw_dp if self.fork_ok else 0
-        self.side_dw_any = st.side_dw_any
-        # adversaries without BatchNorm: both phases of all of them as seven launches (_Plan._build_adversaries_fused)
-        self.adv_fused = st.adv_fused
         self.side_stream = torch.cuda.Stream(device=self.device) if (self.side_dw or self.side_dw_dp) else None
         # adversarial programs: the first branch stream carries the adversaries' passes from the reparameterisation into
         # the backward chain, the decoder's capped weight gradient takes a second one
         self.side_stream2 = torch.cuda.Stream(device=self.device) if (self.side_dw and st.adv_aside >= 2 and st.adv_fused) else None
         self.comm_stream = self.small_stream = self.lane_stream = None
+        self._tune = None  # MMVAE_DP_KERNELS=auto: the kernel-family timing in progress (_dp_autotune)
+        self.dp_tuned: Dict[str, float] = {}
         self._configure_parallel()
         self._sig = self._signature()
+        self._sig_changes = 0  # training steps on which the signature changed (_check_signature)
+        # conditional programs (CondProgram): metadata look-ups shared by an expert's plans, the blocks last stepped
+        self._cond_lookup: Dict[tuple, dict] = {}
+        self._cond_prev_union = None
         self._pending: Dict[str, torch.cuda.Event] = {}
         import weakref
 
@@ -270,9 +324,6 @@ class StepEngine:
         # but only a real run knows how the collectives' resident workgroups treat the static deal, so "auto" times both
         # on the first steps of a multi-rank run and keeps the faster one (_dp_autotune).
         self.dp_kernels = st.dp_kernels
-        if not hasattr(self, "_tune"):
-            self._tune = None
-            self.dp_tuned: Dict[str, float] = {}
         if "MMVAE_X3W" not in os.environ:
             if not mdist.collectives_active():
                 self.lib.mmvae_gemm_set_x3w(-1)
@@ -373,11 +424,10 @@ class StepEngine:
         if sig != self._sig:
             # A captured program freezes the optimiser's hyper-parameters: a per-step schedule (learning-rate warm-up)
             # rebuilds and re-captures every step -- correct, but milliseconds instead of one replay.  Say so once.
-            self._sig_changes = getattr(self, "_sig_changes", 0) + 1
-            if self._sig_changes == 3 and not getattr(self, "_sig_warned", False):
+            self._sig_changes += 1
+            if self._sig_changes == 3:
                 import warnings
 
-                self._sig_warned = True
                 warnings.warn("mmvae_amd.engine: optimiser settings changed on several training steps; every change drops "
                               "the captured step programs and re-captures them (a learning-rate schedule stepping per "
                               "batch costs milliseconds per step) -- change them per epoch, or set use_engine=False")
@@ -466,7 +516,7 @@ class StepEngine:
         could not be read in place: a gene count off a multiple of 4 or a batch off a multiple of 32 (rows-contiguous
         16-byte groups / whole k-tiles: the batch would have to be staged with slack every step -- the reference's
         60 530 / 52 437 genes)."""
-        return bool(self.settings.x_planes or l0_in % 4 != 0 or B % 32 != 0)
+        return l0_in % 4 != 0 or B % 32 != 0
 
     def _select_input(self, x: torch.Tensor, base_key: tuple, needs_slack: bool = True):
         """Plan selection: graphs are keyed by the input pointer once a pointer has been seen twice (resident
@@ -712,7 +762,7 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
         # the previous step computed, and the (expert id, batch) this step computes them for
         self.slabs_ahead, self.prefetch, self.prefetch_slabs = slabs_ahead, prefetch, None
         self.iwae = bool(iwae) and mode == "train"  # opt-in full-IWAE objective (training programs only)
-        self.x = x
+        self.x, self.ldx = x, x.stride(0) if x.shape[0] > 1 else x.shape[1]
         self.R = B * K
         model = eng.model
         m = model.module
@@ -770,13 +820,23 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
         self._ws_bytes = 0
         self._slab_floats = 0
         self._graphs: Optional[list] = None
-        self._probe_next = None         # tag for the next emitted GEMM (measurement hook, see _emit_gemm)
+        self._probe_next = None         # tag for the next emitted GEMM (measurement hook, see _gemm_launch)
         self.probe = None               # dict tag -> [(event, event, flops)] while an eager run is being measured
         self.probe_meta: Dict[str, dict] = {}  # tag -> {work, kernel, cus, bound} of the probed launches (_probed)
         self._forked = False            # the program has branches on other streams
         self._events: List = []         # the fork / join events of the program (kept alive: see _edge)
         self._runs = 0
         self.exp_norm_log = None  # overlapped mode: the expert's pre-clip gradient norm, copied on the comm stream
+        self._x_split_jobs: List = []   # pieces of the split passes (x / the last layer's weights) for forward layer tails
+        self._defer_next_dw = False     # the next bwd_layer leaves its weight gradient to _emit_optimisers (late branch)
+        self._deferred_dw = None        # (GEMM arguments, operand planes) of that weight gradient
+        self._fcws_bytes = 0            # size of the column kernels' shared workspace
+        self._defer_id = 0              # position of the last buffer of a deferred reduction (_next_defer_id)
+        self.x_fp32_dw1 = False         # the first layer's weight gradient reads x as fp32 with dY as planes
+        self.adv_grad_into: Dict[int, torch.Tensor] = {}  # hidden representation -> the adversaries' reversed gradient on it
+        self.n_adv = 0
+        self._label_ring = None         # page-locked slots of the step's class indices (load_labels)
+        self._log_cache: Dict[tuple, list] = {}  # (stage, expert) -> the logging calls of PlanRun.log
         self.metrics = eng.buf("metrics", (256,))
         self.rng_state = rng.state(eng.device)
         cl = getattr(m.vae, "conditionals", None)
@@ -785,53 +845,48 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
             if K != 1:
                 raise _lib.HipLibraryError("engine: conditional layers with the K-sample extension are not supported")
             self.cond = CondProgram(self, cl, eid, train=(mode == "train"))
+        self.layout = plan_layout(
+            eng.settings, fork_ok=eng.fork_ok, side_stream=eng.side_stream is not None,
+            side_stream2=eng.side_stream2 is not None, lane_stream=eng.lane_stream is not None, overlap=eng.overlap,
+            world=eng.world, mode=mode, B=B, K=K, R=self.R, G=self.G, n_in_last=self.dec_layers[-1].n_in, iwae=self.iwae,
+            has_adv=self.has_adv, has_cond=self.cond is not None,
+            adv_reducer=any(o.reducer is not None for o in self.opt_adv))
         self._build()
 
     # ------------------------------------------------------------------------------------------- program building
     def _build(self):
-        eng, lib = self.eng, self.lib
-        B, K, R, Z, G = self.B, self.K, self.R, self.Z, self.G
-        x, ldx = self.x, self.x.stride(0) if self.x.shape[0] > 1 else self.x.shape[1]
-        self.eps = eng.buf("eps", (K, B, Z))
+        """Emit the step's program, phase by phase (branch streams as self.layout places them)."""
+        self.eps = self.eng.buf("eps", (self.K, self.B, self.Z))
         self._mark("step begins (behind the noise fill)")
+        self._plan_operand_planes()
+        self._emit_encoder_forward()
+        self._emit_heads()
+        if self.mode == "embed":  # predict path: the program ends at z
+            return self._finish_forward_only()
+        adv = self._emit_adversaries()
+        loss_calls = self._emit_decoder_forward()
+        if self.mode != "train":  # validation: the program ends with the ELBO terms in the metrics buffer
+            return self._finish_forward_only()
+        self._emit_adversaries_inline(adv)
+        self._emit_decoder_backward(adv, loss_calls)
+        self._emit_encoder_backward()
+        self._emit_optimisers()
+        self._finish(self._mask_layers)
 
-        train = self.mode == "train"
-        # branches beside the latency-bound sections (in-order single-rank program only; see StepEngine.side_dw)
-        # The caps are tuned for the shape where the two weight gradients are SHORTER than the chains they hide behind
-        # (C2: B = 512, K = 1: 105 us of GEMM beside a 190 us chain).  With K samples or bigger batches the GEMMs grow
-        # with the rows while the chains barely do, and a capped GEMM becomes the critical path (measured with the
-        # branches on: C3 4.36 against 4.00 ms, C5 7.03 against 5.93 ms; with adversaries, C4: 1.64 against 1.60 ms).
-        # Small models stay on ONE stream: when the kernels ahead of a fork finish while the host is still enqueuing
-        # the rest of a multi-stream graph, hipGraphLaunch crashes now and then on this runtime (null dereference, box
-        # dependent; only ever seen with the tests' toy shapes, whose whole step is ~100 us -- tools/debug/seg_hunt.sh).
-        # A G-wide weight gradient of >= 5 GFLOP puts the first fork hundreds of microseconds into the replay.
-        big = 2.0 * G * self.dec_layers[-1].n_in * R >= 5e9
-        # The forked program is the default only for the geometry its caps were measured on (C2: a G-wide weight
-        # gradient of ~21 GFLOP, 512 rows: within +-25 %), where it has run > 10^4 replays without a fault; any other
-        # shape stays on one stream unless MMVAE_SIDE_DW_ANY=1 asks for it (the hipGraphLaunch hazard has no
-        # root cause yet, and a crashed replay cannot be recovered in-process).
-        dw_flops = 2.0 * G * self.dec_layers[-1].n_in * R
-        measured = 0.75 * 2.1e10 <= dw_flops <= 1.25 * 2.1e10
-        side_dw = eng.side_dw if (train and eng.side_stream is not None and not eng.overlap and eng.world == 1
-                                  and K == 1 and R <= SIDE_MAX_ROWS and not self.has_adv and big
-                                  and (measured or eng.side_dw_any)) else 0
-        early_branch = bool(side_dw and not self.iwae)  # the small branches: loss words, bias sums, the VAE's optimiser
-        # the late branch alone (the shared VAE's optimiser beside the encoder's capped weight gradient) also serves the
-        # adversarial programs: their branch stream is free again once the adversaries' passes have been joined
-        side_late = bool(side_dw or (eng.side_dw2 and eng.side_stream is not None and train and self.has_adv
-                                     and not eng.overlap and eng.world == 1 and K == 1 and R <= SIDE_MAX_ROWS and big
-                                     and (measured or eng.side_dw_any) and eng.settings.adv_aside))
-        loss_aside, early_calls = False, []
-        # ---- pre-split operands of the G-wide weight gradients (K = 1 training programs on the wave-specialised
-        # kernels): x (split beside the forward chain) and the gradient at the first layer (from its column kernel) feed
-        # dW1 = dY^T x; the last hidden activations (3 MB of planes from their layer tail) are B of dW4 = dP^T h, the wider
-        # operand of that product's tile -- its stagers then split dP only.  (Measured and removed: dP planes from the
-        # reconstruction epilogue -- epilogue +6 us, chain +12 us, no gain; planes of x for the first forward GEMM --
-        # the split pass in front of it costs 17 us for 8 us gained.)
+    def _plan_operand_planes(self):
+        """Pre-split operands of the G-wide weight gradients (K = 1 training programs on the wave-specialised kernels): x
+        (split beside the forward chain) and the gradient at the first layer (from its column kernel) feed dW1 = dY^T x;
+        the last hidden activations (3 MB of planes from their layer tail) are B of dW4 = dP^T h, the wider operand of
+        that product's tile -- its stagers then split dP only.  (Measured and removed: dP planes from the reconstruction
+        epilogue -- epilogue +6 us, chain +12 us, no gain; planes of x for the first forward GEMM -- the split pass in
+        front of it costs 17 us for 8 us gained.)"""
+        eng, lib = self.eng, self.lib
+        B, R, G, train = self.B, self.R, self.G, self.mode == "train"
+        x, ldx = self.x, self.ldx
         l0, lastl = self.enc_layers[0], self.dec_layers[-1]
         pl_on = bool(eng.planes and train and not self.iwae and lib.mmvae_gemm_get_precision() == 1)
         # (any gene count: the planes of x get a leading dimension rounded up to 8, zero columns in between)
-        self.pl_enc = eng._enc_planes(l0.n_in, l0.n_out, l0.bn is not None, B, K, train, self.iwae)
+        self.pl_enc = eng._enc_planes(l0.n_in, l0.n_out, l0.bn is not None, B, self.K, train, self.iwae)
         self.xp = _PlaneBuf(eng, f"xp.{l0.n_in}", B, l0.n_in) if self.pl_enc else None
         self.dYp = _PlaneBuf(eng, f"dYp.{l0.n_out}", B, l0.n_out) if self.pl_enc else None
         self.pl_dec_h = bool(pl_on and lastl.n_in % 8 == 0 and len(self.dec_layers) >= 2
@@ -862,37 +917,37 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
             per = (G + 2) // 3
             wpp, wld, wps = self.wp.args()
             self._x_split_jobs = [(min(per, G - r0), lastl.n_in, _p(lastl.W) + 4 * r0 * lastl.n_in, lastl.n_in,
-                                   wpp + 2 * r0 * wld, wld, wps) for r0 in range(0, G, per)] + getattr(self, "_x_split_jobs", [])
-        # ---- forward, encoder side
-        # (adversarial programs of the measured geometry fork too: the same test as `adv_aside` below)
-        adv_forks = bool(self.has_adv and train and eng.adv_fused and eng.settings.adv_aside >= 2 and eng.side_stream2 is not None
-                         and not eng.overlap and eng.world == 1 and K == 1 and big and (measured or eng.side_dw_any)
-                         and self.cond is None and not any(o.reducer is not None for o in self.opt_adv))
+                                   wpp + 2 * r0 * wld, wld, wps) for r0 in range(0, G, per)] + self._x_split_jobs
 
-        def emit_prefetch():
-            if self.prefetch is None or not train or not (side_dw or adv_forks):
-                return
-            # the NEXT step's first forward product, beside this step's forward chain (no join of its own: the branch
-            # stream is in order and joined ahead of the expert's optimiser -- see the note ahead of the reconstruction launch)
-            eid_n, x_n = self.prefetch
-            ln = _LayerRef(eng.model.module.experts[eid_n].encoder.fc_layers[0], eng.grad_of, False)
-            Bn = x_n.shape[0]
-            sk_n = self._plan_gemm(NT, Bn, ln.n_out, ln.n_in)
-            if ln.bn is None or 2.0 * Bn * ln.n_out * ln.n_in < 5e9:
-                return
-            self.prefetch_slabs = eng.buf(f"prefetch.slabs.{eid_n}", (sk_n, Bn, ln.n_out))
-            self._probe_next = "enc_l1_fwd"
-            self._side_capped_gemm(NT, Bn, ln.n_out, ln.n_in, x_n, x_n.stride(0), ln.W, ln.n_in, self.prefetch_slabs,
-                                   ln.n_out, eng.settings.prefetch_adv if adv_forks else eng.settings.prefetch,
-                                   flags=_lib.GEMM_RAW_SLABS, sk=sk_n, stream=eng.side_stream2 if adv_forks else None)
-            self._probe_next = None
-            self._prefetch_join = True
+    def _emit_prefetch(self):
+        """The NEXT step's first forward product, beside this step's forward chain (StepEngine.training_step).  No join
+        of its own: the branch stream is in order, so the decoder's weight gradient queues behind the product anyway, and
+        the join ahead of the expert's optimiser covers it (a cross-stream join inside the captured program costs ~30 us
+        on this runtime; a product that outlasts the forward chain delays the reconstruction launch's workgroups on the
+        CUs it still holds by its remainder, no more)."""
+        L, eng = self.layout, self.eng
+        if self.prefetch is None or not L.prefetch:
+            return
+        eid_n, x_n = self.prefetch
+        ln = _LayerRef(eng.model.module.experts[eid_n].encoder.fc_layers[0], eng.grad_of, False)
+        Bn = x_n.shape[0]
+        sk_n = self._plan_gemm(NT, Bn, ln.n_out, ln.n_in)
+        if ln.bn is None or 2.0 * Bn * ln.n_out * ln.n_in < 5e9:
+            return
+        self.prefetch_slabs = eng.buf(f"prefetch.slabs.{eid_n}", (sk_n, Bn, ln.n_out))
+        self._probe_next = "enc_l1_fwd"
+        self._gemm_launch(NT, Bn, ln.n_out, ln.n_in, 1.0, x_n, x_n.stride(0), ln.W, ln.n_in, self.prefetch_slabs, ln.n_out,
+                          None, _lib.GEMM_RAW_SLABS, sk=sk_n, cap=L.prefetch_cap,
+                          stream=eng.side_stream2 if L.prefetch_side2 else eng.side_stream)
+        self._probe_next = None
 
-        cur, ld = x, ldx
+    def _emit_encoder_forward(self):
+        B, train = self.B, self.mode == "train"
+        cur, ld = self.x, self.ldx
         if self.slabs_ahead is not None:
             # this step's own first product exists already (the previous step computed it): the next step's starts at
             # once and has the whole forward chain beside it; otherwise it follows this step's own first GEMM
-            emit_prefetch()
+            self._emit_prefetch()
         for i, l in enumerate(self.enc_layers):
             ahead = self.slabs_ahead if i == 0 else None
             if ahead is not None and tuple(ahead.shape) != (self._plan_gemm(NT, B, l.n_out, l.n_in), B, l.n_out):
@@ -905,9 +960,13 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
             if i == 0:
                 self._mark("enc L1 forward done")
                 if self.slabs_ahead is None:
-                    emit_prefetch()
-        q, HV = cur, self.enc_layers[-1].n_out
-        # ---- heads + reparameterisation
+                    self._emit_prefetch()
+
+    def _emit_heads(self):
+        """Mean / variance heads and the fused reparameterisation + KL."""
+        eng, lib = self.eng, self.lib
+        B, K, Z = self.B, self.K, self.Z
+        q, HV = self.enc_layers[-1].d, self.enc_layers[-1].n_out
         self.mu = eng.buf("mu", (B, Z))
         self.a_raw = eng.buf("a_raw", (B, Z))
         self.std = eng.buf("std", (B, Z))
@@ -922,80 +981,74 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
         self._emit(lib.mmvae_reparam_kl_fwd, B, Z, K, _p(self.mu), _p(self.a_raw), _p(self.eps), self.var_eps,
                    _p(self.std), _p(self.z), _p(self.kl_row), _p(self.stat))
         self._mark("reparameterised (fork point)")
-        if self.mode == "embed":  # predict path: the program ends at z
-            return self._finish_forward_only()
         if self.iwae:  # sampled log q(z) - log p(z) per (sample, cell)
             self.logratio = eng.buf("iwae.logratio", (K, B))
             self._emit(lib.mmvae_iwae_logratio, B, Z, K, _p(self.std), _p(self.eps), _p(self.z), _p(self.logratio))
-        # ---- adversaries (fused passes): they read the hidden representations only -- h1 and z exist from here on.  In
-        # the single-rank program of the measured geometry the seven launches of both phases run on the branch stream
-        # beside the decoder's forward and the reconstruction GEMM, and are joined where the backward pass first reads
-        # the reversed gradients; elsewhere they keep their place behind the ELBO.
+
+    def _emit_adversaries(self):
+        """The adversaries' fused passes where they leave the main stream's order: they read the hidden representations
+        only -- h1 and z exist from here on.  In the single-rank program of the measured geometry the launches of both
+        phases run on the branch stream beside the decoder's forward and the reconstruction GEMM, and are joined where the
+        backward pass first reads the reversed gradients; elsewhere they keep their place behind the ELBO
+        (_emit_adversaries_inline).  Returns (hidden representations, their calls or None, on the branch?, as a lane?)."""
+        L, eng = self.layout, self.eng
         hidden = [l.a if l.a is not None else l.d for l in self.enc_layers if l.return_hidden]
         if self.hidden_z:
             hidden.append(self.z)  # first sample (rows 0..B-1)
-        self.adv_grad_into: Dict[int, torch.Tensor] = {}
-        adv_calls, adv_aside = None, False
-        # Under a gradient exchange the adversaries' optimisers cut the program (an all-reduce of each adversary's gradients
-        # in both phases).  Their whole section -- captured segments and exchange points -- then runs as a LANE of its own
-        # on the branch stream, started by the host at this point of the program and joined where the chain reads the
-        # reversed gradients (PlanRun._run_program): its launches and the latency of its four small all-reduces leave the
-        # main stream.  (C4 on one rank with the slice of a world of 8: 1.33 -> see DESIGN section 8.)
-        adv_dp = eng.overlap or any(o.reducer is not None for o in self.opt_adv)
-        adv_lane = False
-        if (self.has_adv and train and eng.adv_fused and adv_dp and eng.settings.adv_aside and eng.lane_stream is not None
-                and K == 1 and self.cond is None):
+        adv_calls, adv_aside, adv_lane = None, False, False
+        if L.adv_lane:
+            # Under a gradient exchange the adversaries' optimisers cut the program (an all-reduce of each adversary's
+            # gradients in both phases).  Their whole section -- captured segments and exchange points -- then runs as a
+            # LANE of its own on the branch stream, started by the host at this point of the program and joined where the
+            # chain reads the reversed gradients (PlanRun._run_program): its launches and the latency of its four small
+            # all-reduces leave the main stream.  (C4 on one rank with the slice of a world of 8: see DESIGN section 8.)
             main_segments, main_cur = self.segments, self._cur
             self.segments, self._cur = [], []
             slot_before = dict(self.metric_slots)
             self._mark("adversaries' lane: first launch")
             built = self._build_adversaries_fused(hidden)
             self._mark("adversaries' lane: done")
+            lane = [it for it in self.segments + [self._cur] if isinstance(it, tuple) or it]
+            self.segments, self._cur = main_segments, main_cur
             if built:
-                lane = [it for it in self.segments + [self._cur] if isinstance(it, tuple) or it]
-                self.segments, self._cur = main_segments, main_cur
                 self._host_marker(("lane", eng.lane_stream, lane))
                 adv_lane = True
             else:
-                self.segments, self._cur = main_segments, main_cur
                 self.metric_slots = slot_before
-        if self.has_adv and train and eng.adv_fused and not adv_dp:
+        if self.has_adv and self.mode == "train" and eng.settings.adv_fused and not self._adv_dp():
             start = len(self._cur)
             if self._build_adversaries_fused(hidden):
                 adv_calls = self._take(start)
                 adv_calls = [c for c in [self._mark_call("adversaries: first launch")] if c] + adv_calls + \
                             [c for c in [self._mark_call("adversaries: done")] if c]
-                adv_aside = bool(eng.settings.adv_aside and eng.side_stream is not None and not eng.overlap
-                                 and eng.world == 1 and K == 1 and big and (measured or eng.side_dw_any)
-                                 and self.cond is None)
+                adv_aside = L.adv_aside
                 if adv_aside:
                     self._fork()
-        # ---- forward, decoder side (rows R = K*B)
+        return hidden, adv_calls, adv_aside, adv_lane
+
+    def _adv_dp(self) -> bool:
+        """Are the adversaries' gradients exchanged (data parallelism)?"""
+        return self.eng.overlap or any(o.reducer is not None for o in self.opt_adv)
+
+    def _emit_decoder_forward(self) -> list:
+        """Decoder forward (rows R = K*B), the reconstruction launch and the ELBO terms.  Returns the loss-word launches
+        taken off the main stream (the early branch), if any."""
+        eng, lib, L = self.eng, self.lib, self.layout
+        B, K, R, Z, G, train = self.B, self.K, self.R, self.Z, self.G, self.mode == "train"
         cur, ld = self.z, Z
         if self.cond is not None:  # CLVAE.after_reparameterize: the sample passes through the conditional layers
             cur, ld = self.cond.emit_forward(self.z)
         for i, l in enumerate(self.dec_layers[:-1]):
+            to_planes = self.hp is not None and K == 1 and i == len(self.dec_layers) - 2
             cur = self.fwd_layer(f"{self.eid}.dec{i}.K{K}", l, cur, ld, R, training=train,
-                                 mask_stream=len(self.enc_layers) + i,
-                                 planes_out=self.hp if (self.hp is not None and K == 1 and i == len(self.dec_layers) - 2) else None,
-                                 split_job=None if (self.hp is not None and K == 1 and i == len(self.dec_layers) - 2)
-                                 else self._next_x_split_job(l, R))
+                                 mask_stream=len(self.enc_layers) + i, planes_out=self.hp if to_planes else None,
+                                 split_job=None if to_planes else self._next_x_split_job(l, R))
             ld = l.n_out
-        for job in getattr(self, "_x_split_jobs", []):  # tails the chain did not have: passes of their own
+        for job in self._x_split_jobs:  # tails the chain did not have: passes of their own
             self._emit(lib.mmvae_split_planes_f32, *job)
         self._x_split_jobs = []
-        if getattr(self, "_prefetch_join", False) and eng.settings.prefetch_join:
-            # (diagnostics) join the next step's product ahead of the reconstruction launch.  Default: no join here -- a
-            # cross-stream join inside the captured program costs ~30 us on this runtime; the branch stream is in order,
-            # so the decoder's weight gradient queues behind the product anyway, and the join ahead of the expert's
-            # optimiser covers it.  A product that outlasts the forward chain delays the reconstruction launch's
-            # workgroups on the CUs it still holds by its remainder, no more.
-            self._mark("forward chain done (prefetch joined)")
-            self._join()
-        self._prefetch_join = False
         last = self.dec_layers[-1]
-        fused_last = last.relu and last.bn is None and last.p == 0
-        if not fused_last:
+        if not (last.relu and last.bn is None and last.p == 0):
             raise _lib.HipLibraryError("engine: the last decoder layer must be Linear+ReLU (fused recon epilogue)")
         last.inp, last.ld_inp, last.rows = cur, ld, R
         T = lib.mmvae_recon_tiles(G)
@@ -1004,7 +1057,7 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
         # over whole k-tiles instead of a tail slab on the element-guarded kernel (12 us + a launch boundary per step).
         # The weight rows "beyond" W that those zero columns meet are the decoder bias behind it in the arena (finite).
         Gp = (G + 31) // 32 * 32
-        if not (train and Gp != G and big and lib.mmvae_gemm_get_precision() == 1
+        if not (train and Gp != G and L.big and lib.mmvae_gemm_get_precision() == 1
                 and (Gp - G) * last.n_in <= last.b.numel() + 32
                 and last.b.data_ptr() == last.W.data_ptr() + 4 * last.W.numel()):
             Gp = G
@@ -1034,8 +1087,8 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
             self._sum_jobs, self._gemm_jobs = pending, pending_g
             h_in, ld_h, kpad = hpad, Kp, True
         self._emit(lib.mmvae_decoder_recon_rows_colsum_f32, R, B, G, last.n_in, _p(h_in), ld_h, _p(last.W), last.n_in,
-                   _p(last.b), _p(x), ldx, None, 0, _p(self.dP), self.ldp, _p(self.se_part), _p(self.dp_colpart),
-                   probe=("dec_l2_recon", 2.0 * R * G * last.n_in))
+                   _p(last.b), _p(self.x), self.ldx, None, 0, _p(self.dP), self.ldp, _p(self.se_part),
+                   _p(self.dp_colpart), probe=("dec_l2_recon", 2.0 * R * G * last.n_in))
         if kpad:  # the launch state brackets the launch
             launch = self._cur.pop()
 
@@ -1055,37 +1108,41 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
             self.rows3 = eng.buf("iwae.rows3", (3, B))
             self._emit(lib.mmvae_elbo_finalize_iwae, B, K, T, _p(self.se_part), _p(self.logratio), _p(self.stat), Z,
                        _p(eng.klw_dev), 1.0, _p(self.metrics), _p(self.w), _p(self.rows3))
-        else:
-            if early_branch and not self.has_adv:
-                # K = 1: the backward pass starts from dP, which the reconstruction epilogue has already written; the
-                # loss words are only logged -- their two launches leave the critical path
-                loss_aside = True
-            start = len(self._cur)
-            self._emit(lib.mmvae_elbo_finalize, B, K, T, _p(self.se_part), _p(self.kl_row), _p(self.stat), Z,
-                       _p(eng.klw_dev), 1.0, _p(self.metrics), _p(self.w), _p(self.recon_row))
-            if loss_aside:
-                early_calls = self._take(start)
-        if not train:  # validation: the program ends with the ELBO terms in the metrics buffer
-            return self._finish_forward_only()
-        # ---- adversarial phases: total loss = ELBO loss + adv_weight * sum of the generator-phase losses
-        # (cmmvae_model.py:182-184; without adversaries it IS the ELBO loss word: no launch)
-        self.dz_lat = eng.buf("dz_lat", (R, Z))
+            return []
+        start = len(self._cur)
+        self._emit(lib.mmvae_elbo_finalize, B, K, T, _p(self.se_part), _p(self.kl_row), _p(self.stat), Z,
+                   _p(eng.klw_dev), 1.0, _p(self.metrics), _p(self.w), _p(self.recon_row))
+        # K = 1: the backward pass starts from dP, which the reconstruction epilogue has already written; the loss words
+        # are only logged -- their two launches leave the critical path
+        return self._take(start) if (L.early and not self.has_adv) else []
+
+    def _emit_adversaries_inline(self, adv):
+        """Total loss = ELBO loss + adv_weight * sum of the generator-phase losses (cmmvae_model.py:182-184; without
+        adversaries it IS the ELBO loss word: no launch), and the adversaries' passes that stay in the main program."""
+        hidden, adv_calls, adv_aside, adv_lane = adv
+        eng, lib = self.eng, self.lib
+        total = lambda beta: self._emit(lib.mmvae_axpby, 1, 1.0, _p(self.metrics), beta, self.mptr("total_loss"))  # noqa: E731
+        self.dz_lat = eng.buf("dz_lat", (self.R, self.Z))
         if not self.has_adv:
             self.metric_slots["total_loss"] = 0
         elif adv_lane:
-            pass  # (joined below, where the chain first reads the reversed gradients)
-        elif adv_calls is None and eng.adv_fused and adv_dp and self._build_adversaries_fused(hidden):
-            self._emit(lib.mmvae_axpby, 1, 1.0, _p(self.metrics), 1.0, self.mptr("total_loss"))
+            pass  # (joined in the decoder's backward pass, where the chain first reads the reversed gradients)
+        elif adv_calls is None and eng.settings.adv_fused and self._adv_dp() and self._build_adversaries_fused(hidden):
+            total(1.0)
         elif adv_calls is None:  # per-layer program: the slot starts as the ELBO loss, every generator phase adds to it
-            self._emit(lib.mmvae_axpby, 1, 1.0, _p(self.metrics), 0.0, self.mptr("total_loss"))
+            total(0.0)
             self._build_adversaries(hidden)
         elif adv_aside:  # (emitted behind the main-stream work it runs beside: the executor enqueues in emission order)
             self._branch(eng.side_stream, adv_calls)
         else:
             self._cur.extend(adv_calls)
-            self._emit(lib.mmvae_axpby, 1, 1.0, _p(self.metrics), 1.0, self.mptr("total_loss"))
+            total(1.0)
 
-        # ---- backward, decoder side
+    def _emit_decoder_backward(self, adv, loss_calls):
+        eng, lib, L = self.eng, self.lib, self.layout
+        B, K, R, Z, G = self.B, self.K, self.R, self.Z, self.G
+        _, _, adv_aside, adv_lane = adv
+        last = self.dec_layers[-1]
         dw_inp, dw_ld, w_rows = last.inp, last.ld_inp, None
         if K > 1:
             # The gradient at the decoder's output is diag(w) dP (w = softmax weights of the K-sample bound, known only
@@ -1103,61 +1160,33 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
             self._emit(lib.mmvae_scale_rows, R, last.n_in, _p(last.inp), last.ld_inp, _p(self.w), _p(dw_inp), dw_ld)
             if self.hp is not None:  # B of the weight gradient as planes: of the SCALED activations (a 21 + 31 MB pass at C3)
                 self._emit(lib.mmvae_split_planes_f32, R, last.n_in, _p(dw_inp), dw_ld, *self.hp.args())
-        dw_pl = (None, self.hp) if self.pl_dec_h else None
-        # (adversaries on the first branch stream: the capped weight gradient beside the chain takes the second one)
-        dw_stream = eng.side_stream2 if adv_aside else None
-        dw4_late = None
-        if adv_aside and dw_stream is not None and eng.settings.adv_aside >= 2:
+        # The decoder's G-wide weight gradient (dW = dP^T h, ~105 us at C2, needed by the optimiser only) where a branch
+        # takes it: the input gradient first (the chain waits for it), the weight gradient capped beside the chain.
+        late_dw = adv_aside and L.adv_dw2
+        if late_dw:
             # The branch stream carries the adversaries until the chain needs their reversed gradients; the weight
             # gradient is forked THERE, on a second branch beside the rest of the chain (reparameterisation, heads, the
             # encoder's BatchNorm layers: ~105 us), capped to the workgroup count that keeps its 500 work items at
             # three rounds.  C4 on one box: 1.183 -> 1.135 ms at 185, 1.132 at 170; 1.17 at 125, 1.20 at 150, 1.16 at
             # 200.  Forked right behind the input gradient instead -- beside the adversaries' generator phase -- the
             # step is 8 % SLOWER (1.25 ms): the three lanes fight over the CUs (profiles/r4_c4_dw_aside.txt).
-            self._probe_next = "dec_l2_dx"
-            S = self.gemm_raw(NN, R, last.n_in, self.ldp, self.dP, self.ldp, last.W, last.n_in)
-            self._probe_next = None
+            S = self._emit_dec_dx()
             self._mark("decoder dX done")
-
-            def dw4_late():
-                self._probe_next = "dec_l2_dw"
-                if not self._fuse_sqnorm(TN, G, last.n_in, self.kpad(R), 1.0, self.dP, self.ldp, last.inp, last.ld_inp, last.gW,
-                                         last.n_in, None, 0, side_cap=ADV_DW_CAP, planes=dw_pl, stream=dw_stream):
-                    self.gemm(TN, G, last.n_in, self.kpad(R), self.dP, self.ldp, last.inp, last.ld_inp, last.gW, last.n_in,
-                              side=True, planes=dw_pl)
-                self._probe_next = None
-        elif side_dw:  # input gradient first (the chain waits for it), then the weight gradient on the side branch
-            self._probe_next = "dec_l2_dx"
-            S = self.gemm_raw(NN, R, last.n_in, self.ldp, self.dP, self.ldp, last.W, last.n_in)
-            self._probe_next = "dec_l2_dw"
-            if not self._fuse_sqnorm(TN, G, last.n_in, self.kpad(R), 1.0, self.dP, self.ldp, last.inp, last.ld_inp, last.gW,
-                                     last.n_in, None, 0, side_cap=side_dw, planes=dw_pl):
-                self.gemm(TN, G, last.n_in, self.kpad(R), self.dP, self.ldp, last.inp, last.ld_inp, last.gW, last.n_in, side=True,
-                          planes=dw_pl)
-            self._probe_next = None
+        elif L.side_dw:  # beside the backward chain of the core layers (~150 us of latency-bound launches)
+            S = self._emit_dec_dx()
+            self._emit_dec_dw(last.inp, last.ld_inp, cap=L.side_dw)
             self._mark("decoder dX done")
-            if early_branch:  # behind the weight gradient on its stream: one branch, in order (probe: DESIGN.md 5)
+            if L.early:  # behind the weight gradient on its stream: one branch, in order (probe: DESIGN.md 5)
                 self._fork()  # (the weight gradient may have stayed on the main stream)
-                self._branch(eng.side_stream, early_calls + [c for c in [self._mark_call("decoder dW + loss words done (branch)")] if c])
-        elif (eng.side_dw_dp and eng.overlap and eng.side_stream is not None and train and K == 1 and not self.has_adv
-              and big and (measured or eng.side_dw_any) and self.cond is None
-              and self._plan_gemm(TN, G, last.n_in, self.kpad(R)) == 1):
-            # exchange program: input gradient first, the weight gradient capped on the side stream beside the chain up
-            # to the VAE's exchange point (the cut there joins it)
-            self._probe_next = "dec_l2_dx"
-            S = self.gemm_raw(NN, R, last.n_in, self.ldp, self.dP, self.ldp, last.W, last.n_in)
-            self._probe_next = "dec_l2_dw"
-            self._side_capped_gemm(TN, G, last.n_in, self.kpad(R), self.dP, self.ldp, last.inp, last.ld_inp, last.gW, last.n_in,
-                                   eng.side_dw_dp, planes=dw_pl)
-            self._probe_next = None
+                self._branch(eng.side_stream, loss_calls + [c for c in [self._mark_call("decoder dW + loss words done (branch)")] if c])
+        elif L.dp_dw and self._plan_gemm(TN, G, last.n_in, self.kpad(R)) == 1:
+            # exchange program: capped on the side stream beside the chain up to the VAE's exchange point (the cut there
+            # joins it)
+            S = self._emit_dec_dx()
+            self._emit_dec_dw(last.inp, last.ld_inp, cap=L.dp_dw, exchange=True)
         else:
-            self._probe_next = "dec_l2_dw" if big else None
-            self.gemm(TN, G, last.n_in, self.kpad(R), self.dP, self.ldp, dw_inp, dw_ld, last.gW, last.n_in, side=True,
-                      planes=dw_pl)
-            self._probe_next = "dec_l2_dx" if big else None
-            S = self.gemm_raw(NN, R, last.n_in, self.ldp, self.dP, self.ldp, last.W, last.n_in,
-                              planes=(None, self.wp) if self.pl_dec_w else None)
-            self._probe_next = None
+            self._emit_dec_dw(dw_inp, dw_ld, probe=L.big)
+            S = self._emit_dec_dx(probe=L.big, planes=(None, self.wp) if self.pl_dec_w else None)
         rest = self.dec_layers[:-1]
         for j in range(len(rest) - 1, -1, -1):
             l = rest[j]
@@ -1169,32 +1198,59 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
                                dx_out=self.dz_lat if self.cond is None else self.cond.d_out)
         if self.cond is not None:
             self.cond.emit_backward(self.dz_lat)
-            if mdist.collectives_active() and train:
+            if mdist.collectives_active():
                 # blocks another rank saw and this one did not: zeros into the exchange (job table of this step)
                 self._emit(lib.mmvae_grad_zero_flagged_jobs, self.cond.max_jobs, self.cond.jobs_ptr,
                            _p(self.cond.opt.arena.grad))
         if not rest:
             raise _lib.HipLibraryError("engine: decoder needs at least two layers")
-        if adv_lane:
+        if adv_lane or adv_aside:  # the adversaries' reversed gradients are read from here on
             self._mark("chain reaches the adversaries' join")
-            self._host_marker(("lane_join", eng.lane_stream))
+            if adv_lane:
+                self._host_marker(("lane_join", eng.lane_stream))
+            else:
+                self._join(only=eng.side_stream)
             self._mark("adversaries joined")
-            self._emit(lib.mmvae_axpby, 1, 1.0, _p(self.metrics), 1.0, self.mptr("total_loss"))
-        if adv_aside:  # the adversaries' branch: its reversed gradients are read from here on
-            self._mark("chain reaches the adversaries' join")
-            self._join(only=eng.side_stream)
-            self._mark("adversaries joined")
-            if dw4_late is not None:
-                dw4_late()
+            if late_dw:
+                self._emit_dec_dw(last.inp, last.ld_inp, cap=ADV_DW_CAP, stream=eng.side_stream2)
                 c = self._mark_call("decoder dW done (second branch)")
                 if c is not None:
-                    self._branch(dw_stream, [c])
+                    self._branch(eng.side_stream2, [c])
             self._emit(lib.mmvae_axpby, 1, 1.0, _p(self.metrics), 1.0, self.mptr("total_loss"))
         # gradient-reversed adversary gradient on z (first sample) joins here
         zi = self.adv_grad_into.get(id(self.z))
         if zi is not None:
             self._emit(lib.mmvae_axpby, B * Z, 1.0, _p(zi), 1.0, _p(self.dz_lat))
-        # ---- reparameterisation + heads backward
+
+    def _emit_dec_dx(self, probe: bool = True, planes=None) -> int:
+        """Input gradient of the decoder's last layer, dP . W, as raw split-K slabs; returns their count."""
+        last = self.dec_layers[-1]
+        self._probe_next = "dec_l2_dx" if probe else None
+        S = self.gemm_raw(NN, self.R, last.n_in, self.ldp, self.dP, self.ldp, last.W, last.n_in, planes=planes)
+        self._probe_next = None
+        return S
+
+    def _emit_dec_dw(self, inp, ld_inp, cap: int = 0, stream=None, exchange: bool = False, probe: bool = True):
+        """Weight gradient of the decoder's last layer, dP^T h, into the gradient arena: capped to `cap` workgroups on a
+        branch stream (`stream`, default the side stream) -- with the norm partials of its epilogue where it can leave
+        them, not in the exchange program (the norm is that of the REDUCED gradients there) -- or (cap 0) in order."""
+        last = self.dec_layers[-1]
+        args = (TN, self.G, last.n_in, self.kpad(self.R))
+        ops = (self.dP, self.ldp, inp, ld_inp, last.gW, last.n_in)
+        planes = (None, self.hp) if self.pl_dec_h else None
+        self._probe_next = "dec_l2_dw" if probe else None
+        if exchange:
+            self._gemm_launch(*args, 1.0, *ops, None, 0, planes=planes, cap=cap, stream=self.eng.side_stream)
+        elif not (cap and self._fuse_sqnorm(*args, 1.0, *ops, None, 0, side_cap=cap, planes=planes, stream=stream)):
+            self.gemm(*args, *ops, side=True, planes=planes)
+        self._probe_next = None
+
+    def _emit_encoder_backward(self):
+        """Reparameterisation and heads backward, then the encoder's layers (the VAE's gradient exchange begins where its
+        gradients are final)."""
+        eng, lib = self.eng, self.lib
+        B, K, Z = self.B, self.K, self.Z
+        q, HV = self.enc_layers[-1].d, self.enc_layers[-1].n_out
         dm = eng.buf("dmu_da", (2, B, Z))  # one buffer: the two heads' bias column sums are one pass over [2B, Z]
         self.dmu, self.da = dm[0], dm[1]
         dq2 = eng.buf("dq", (2, B, HV))    # one slab per head: the next layer's tail sums them on the fly
@@ -1217,7 +1273,6 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
                 self._emit_fc_bwd(B, Z, dy, None, None, None, eng.grad_of(lin.bias))
         for dy, lin in ((self.dmu, self.mean_enc), (self.da, self.var_enc)):
             self.gemm(TN, Z, HV, self.kpad(B), dy, Z, q, HV, eng.grad_of(lin.weight), HV, side=True)
-        # ---- backward, encoder side
         if self._gemm_group([(NN, B, HV, Z, self.dmu, Z, self.mean_enc.weight, HV, dq2[0], HV, None, 0, 1.0),
                              (NN, B, HV, Z, self.da, Z, self.var_enc.weight, HV, dq2[1], HV, None, 0, 1.0)]):
             din, S = dq2, 2
@@ -1232,7 +1287,7 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
             l = self.enc_layers[j]
             hid = l.a if l.a is not None else l.d
             addend = self.adv_grad_into.get(id(hid)) if l.return_hidden else None
-            if j == 0 and side_late:
+            if j == 0 and self.layout.late:
                 self._defer_next_dw = True
             S_next = self.bwd_layer(l, din, S, addend=addend, need_dx="raw" if j > 0 else "none",
                                     dz_planes=self.dYp if (j == 0 and self.pl_enc) else None,
@@ -1241,21 +1296,23 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
             if early and j == self.n_expert_enc:  # the last VAE layer is done: what remains is the expert's encoder
                 self._begin_exchange(self.opt_vae)
         self._mark("backward chain done")
-        # ---- clip + Adam (reference order: clip vae, clip expert, step vae, step expert)
-        # Logged scalars: the step's metrics words (and the pre-clip gradient norms) are copied into a buffer of this
-        # plan's own as the last node(s) of the captured program -- the logged tensors are views of it, valid until
-        # this plan's next step -- instead of three D2D copies issued by the host behind every replay (~24 us).
+
+    def _emit_optimisers(self):
+        """Clip + Adam (reference order: clip vae, clip expert, step vae, step expert) and the copy of the logged scalars.
+        Logged scalars: the step's metrics words (and the pre-clip gradient norms) are copied into a buffer of this
+        plan's own as the last node(s) of the captured program -- the logged tensors are views of it, valid until this
+        plan's next step -- instead of three D2D copies issued by the host behind every replay (~24 us)."""
+        eng, lib, L = self.eng, self.lib, self.layout
         self.log_buf = torch.zeros(256, dtype=torch.float32, device=eng.device)
 
         def emit_log_copy():
             self._emit(lib.mmvae_axpby, 256, 1.0, _p(self.metrics), 0.0, _p(self.log_buf))
 
-        dw = getattr(self, "_deferred_dw", None)
-        self._deferred_dw = None
-        late_branch = bool(side_late and dw is not None and self.cond is None)
+        early = eng.overlap
+        deferred, self._deferred_dw = self._deferred_dw, None
+        late_branch = bool(L.late and deferred is not None and self.cond is None)
         start = len(self._cur)
-        self.optimizer(self.opt_vae, self.clip_vae, exchange="wait" if early else "inline",
-                       join=not late_branch)
+        self.optimizer(self.opt_vae, self.clip_vae, exchange="wait" if early else "inline", join=not late_branch)
         self.log_norm(self.opt_vae, "grad_norms/vae")
         if late_branch:
             # the shared VAE's clip + Adam (a chain of small launches) beside the expert encoder's G-wide weight
@@ -1266,18 +1323,16 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
             # profiles/r2_branch_order.txt).
             calls = self._take(start)
             self._fork()  # the branch depends on the chain up to here; its kernels are enqueued behind the GEMM
-            layout, M, N, Kk, A, lda, Bm, ldb, Cm, ldc = dw
-            dwp = getattr(self, "_deferred_dw_planes", None)
+            (layout, M, N, Kk, A, lda, Bm, ldb, Cm, ldc), dwp = deferred
             self._probe_next = "enc_l1_dw"
-            if not self._fuse_sqnorm(layout, M, N, Kk, 1.0, A, lda, Bm, ldb, Cm, ldc, None, 0, side_cap=eng.side_dw2,
+            if not self._fuse_sqnorm(layout, M, N, Kk, 1.0, A, lda, Bm, ldb, Cm, ldc, None, 0, side_cap=L.late_cap,
                                      on_side=False, planes=dwp):
-                self.gemm(*dw, side=True, planes=dwp)
+                self.gemm(*deferred[0], side=True, planes=dwp)
             self._probe_next = None
             self._branch(eng.side_stream, calls + [c for c in [self._mark_call("VAE optimiser done (branch)")] if c])
-        elif dw is not None:
-            dwp = getattr(self, "_deferred_dw_planes", None)
-            self._probe_next = "enc_l1_dw" if big else None
-            self.gemm(*dw, side=True, planes=dwp)
+        elif deferred is not None:
+            self._probe_next = "enc_l1_dw" if L.big else None
+            self.gemm(*deferred[0], side=True, planes=deferred[1])
             self._probe_next = None
         if early:  # the expert's exchange + update leave the main stream: its norm is logged from the comm stream
             emit_log_copy()
@@ -1296,49 +1351,38 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
             self.log_norm(self.opt_exp, "grad_norms/expert")
             if not ride:
                 emit_log_copy()
-        self.segments.append(self._cur)
-        self._cur = []
-        # noise: Philox fills (production) or explicit buffers (parity mode), at the head of the program
-        if not self.explicit:
-            n_max = K * B * Z
-            fills = []  # every keep-mask and the rsample noise of the step: one launch (same numbers as one fill each)
-            for l, stream in self._mask_layers:  # expert / VAE layers and both phases of every adversary
-                n_max = max(n_max, l.mask.numel())
-                fills.append(_lib.PhiloxJob(_p(l.mask), l.mask.numel(), rng.STREAM_DROPOUT + stream, l.p, 0))
-            fills.append(_lib.PhiloxJob(_p(self.eps), K * B * Z, rng.STREAM_NORMAL, 0.0, 1))
-            arr = (_lib.PhiloxJob * len(fills))(*fills)
-            jobs_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(eng.device)
-            self._job_tables.append(jobs_dev)
-            # (one launch: the fill's last workgroup -- a ticket -- advances the Philox counter)
-            ticket = eng.buf("philox.ticket", (1,), torch.int32)
-            self._emit(lib.mmvae_philox_fill_jobs_advance, len(fills), jobs_dev.data_ptr(), n_max, _p(self.rng_state),
-                       (n_max + 3) // 4, _p(ticket))
-            self.segments[0] = self._cur + self.segments[0]
-            self._cur = []
-        self._size_workspaces()
 
     def _finish_forward_only(self):
-        """Close a forward-only program: rsample noise at its head, shared workspaces sized."""
-        eng, lib = self.eng, self.lib
+        """Close a forward-only program."""
         self.exp_norm_log = None
         self.has_adv = False
+        self._finish([])
+
+    def _finish(self, masks):
+        """Close the program: the step's noise at its head -- one Philox launch for every keep mask in `masks` and the
+        rsample noise, unless parity mode loads explicit buffers -- and the shared workspaces sized."""
+        eng, lib = self.eng, self.lib
         self.segments.append(self._cur)
         self._cur = []
         if not self.explicit:
-            n = self.K * self.B * self.Z
-            # (one launch: the fill's last workgroup advances the counter)
-            arr = (_lib.PhiloxJob * 1)(_lib.PhiloxJob(_p(self.eps), n, rng.STREAM_NORMAL, 0.0, 1))
-            jobs_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(eng.device)
-            self._job_tables.append(jobs_dev)
-            self._emit(lib.mmvae_philox_fill_jobs_advance, 1, jobs_dev.data_ptr(), n, _p(self.rng_state),
-                       (n + 3) // 4, _p(eng.buf("philox.ticket", (1,), torch.int32)))
+            n_max = self.K * self.B * self.Z
+            fills = []
+            for l, stream in masks:  # expert / VAE layers and both phases of every adversary
+                n_max = max(n_max, l.mask.numel())
+                fills.append(_lib.PhiloxJob(_p(l.mask), l.mask.numel(), rng.STREAM_DROPOUT + stream, l.p, 0))
+            fills.append(_lib.PhiloxJob(_p(self.eps), self.K * self.B * self.Z, rng.STREAM_NORMAL, 0.0, 1))
+            jobs = self._upload_table((_lib.PhiloxJob * len(fills))(*fills))
+            # (one launch: the fill's last workgroup -- a ticket -- advances the Philox counter)
+            ticket = eng.buf("philox.ticket", (1,), torch.int32)
+            self._emit(lib.mmvae_philox_fill_jobs_advance, len(fills), jobs, n_max, _p(self.rng_state), (n_max + 3) // 4,
+                       _p(ticket))
             self.segments[0] = self._cur + self.segments[0]
             self._cur = []
         self._size_workspaces()
 
     def _size_workspaces(self):
         eng = self.eng
-        self.fcws = eng.buf("fc_ws", (max(getattr(self, "_fcws_bytes", 0) // 4, 1),))
+        self.fcws = eng.buf("fc_ws", (max(self._fcws_bytes // 4, 1),))
         for key, t in eng._pool.items():
             if key[0] == "fc_ws" and t.numel() > self.fcws.numel():
                 self.fcws = t

@@ -25,7 +25,6 @@ class PlanAdversaries:
         if not pairs or not (1 <= H <= _lib.ADV_MAX_HEADS):
             return False
         g = eng.grad_of
-        pad4 = lambda c: (c + 3) // 4 * 4  # noqa: E731
         nets, mask_refs = [], []
         for i, (h, adv) in enumerate(pairs, start=1):
             opt = self.opt_adv[i - 1]
@@ -34,18 +33,11 @@ class PlanAdversaries:
                 return False
             n_e = lins[0].in_features
             a = opt.arena
-            if H > 1:  # the heads as ONE matrix / bias vector of the arena (HipAdam pack=): rows padded to 4 per head
-                ws, bs = [l.weight for l in lins], [l.bias for l in lins]
-                rows_of = [pad4(l.out_features) for l in lins]
-                chain = lambda ts, per_row: all(ts[k + 1].data_ptr() == ts[k].data_ptr() + 4 * rows_of[k] * per_row  # noqa: E731
-                                                for k in range(H - 1))
-                if not (chain(ws, n_e) and chain(bs, 1) and chain([g(w) for w in ws], n_e) and chain([g(b) for b in bs], 1)):
+            if H > 1:
+                packed = self._packed_heads(opt, lins, n_e)
+                if packed is None:
                     return False
-                Ct = sum(rows_of)
-                ow, ob = a.offsets[arena_of(ws[0])[1]], a.offsets[arena_of(bs[0])[1]]
-                Wh, bh = a.data[ow:ow + Ct * n_e].view(Ct, n_e), a.data[ob:ob + Ct]
-                gWh, gbh = a.grad[ow:ow + Ct * n_e].view(Ct, n_e), a.grad[ob:ob + Ct]
-                col = [sum(rows_of[:k]) for k in range(H)]
+                Wh, bh, gWh, gbh, col = (packed[k] for k in ("W", "b", "gW", "gb", "col"))
             else:
                 Wh, bh, gWh, gbh, col = lins[0].weight, lins[0].bias, g(lins[0].weight), g(lins[0].bias), [0]
             layers, covered = [], {id(l.weight) for l in lins} | {id(l.bias) for l in lins}
@@ -140,21 +132,10 @@ class PlanAdversaries:
             # heads laid out back to back in the optimiser arena (HipAdam pack=): ONE matrix [sum of classes, n_e] and
             # one bias vector -> forward, bias gradient, weight gradient and input gradient of all heads are one launch
             # each instead of one per head (and the input gradient loses its accumulate chain)
-            fused = None
-            lins = [heads[c] for c in self.conditions]
-            if H > 1:
-                ws, bs = [l.weight for l in lins], [l.bias for l in lins]
-                pad4 = lambda c: (c + 3) // 4 * 4
-                rows_of = [pad4(l.out_features) for l in lins]  # class counts padded to 4 (HipAdam pack alignment)
-                chain = lambda ts, per_row: all(ts[k + 1].data_ptr() == ts[k].data_ptr() + 4 * rows_of[k] * per_row
-                                                for k in range(H - 1))
-                if (chain(ws, n_e) and chain(bs, 1) and chain([g(w) for w in ws], n_e) and chain([g(b) for b in bs], 1)):
-                    Ct = sum(rows_of)
-                    a, iw, ib = opt.arena, arena_of(ws[0])[1], arena_of(bs[0])[1]
-                    ow, ob = a.offsets[iw], a.offsets[ib]
-                    fused = dict(Ct=Ct, W=a.data[ow:ow + Ct * n_e].view(Ct, n_e), b=a.data[ob:ob + Ct],
-                                 gW=a.grad[ow:ow + Ct * n_e].view(Ct, n_e), gb=a.grad[ob:ob + Ct],
-                                 logits=eng.buf(f"adv{i}.logits_all", (B, Ct)), dlogits=eng.buf(f"adv{i}.dlogits_all", (B, Ct)))
+            fused = self._packed_heads(opt, [heads[c] for c in self.conditions], n_e) if H > 1 else None
+            if fused is not None:
+                fused.update(logits=eng.buf(f"adv{i}.logits_all", (B, fused["Ct"])),
+                             dlogits=eng.buf(f"adv{i}.dlogits_all", (B, fused["Ct"])))
             for phase in ("discriminator", "generator"):
                 gen = phase == "generator"
                 layers = phase_layers[phase]
@@ -228,6 +209,25 @@ class PlanAdversaries:
                     self.optimizer(opt, self.clip_adv)
                     self.log_norm(opt, f"grad_norms/discriminator_{i}", final=False)
 
+    def _packed_heads(self, opt, lins, n_e: int):
+        """The heads of one adversary laid out back to back in its optimiser's arena (HipAdam pack=: class counts padded
+        to 4 rows per head) as ONE matrix [Ct, n_e] and one bias vector: dict(Ct, W, b, gW, gb, col = each head's first
+        row), or None when they are not."""
+        g = self.eng.grad_of
+        ws, bs = [l.weight for l in lins], [l.bias for l in lins]
+        rows_of = [(l.out_features + 3) // 4 * 4 for l in lins]
+
+        def chain(ts, per_row):
+            return all(ts[k + 1].data_ptr() == ts[k].data_ptr() + 4 * rows_of[k] * per_row for k in range(len(ts) - 1))
+
+        if not (chain(ws, n_e) and chain(bs, 1) and chain([g(w) for w in ws], n_e) and chain([g(b) for b in bs], 1)):
+            return None
+        Ct, a = sum(rows_of), opt.arena
+        ow, ob = a.offsets[arena_of(ws[0])[1]], a.offsets[arena_of(bs[0])[1]]
+        return dict(Ct=Ct, W=a.data[ow:ow + Ct * n_e].view(Ct, n_e), b=a.data[ob:ob + Ct],
+                    gW=a.grad[ow:ow + Ct * n_e].view(Ct, n_e), gb=a.grad[ob:ob + Ct],
+                    col=[sum(rows_of[:k]) for k in range(len(lins))])
+
     # ------------------------------------------------------------------------------------------------ execution
     def load_labels(self, metadata):
         """The step's class indices: metadata columns -> int64 through the class-level Adversarial.labels tables
@@ -239,7 +239,7 @@ class PlanAdversaries:
         n = len(metadata)
         if n != self.B:
             raise ValueError(f"engine: metadata has {n} rows, the batch has {self.B}")
-        if getattr(self, "_label_ring", None) is None:
+        if self._label_ring is None:
             self._label_ring = _PinnedRing(len(self.conditions) * self.B, torch.int64)
             self._labels_all = self.eng.buf("labels.all", (len(self.conditions), self.B), torch.int64)
             self._labels_tmp = np.zeros(self.B, dtype=np.int32)

@@ -91,7 +91,7 @@ class CondProgram:
             b_idx = np.array([arena_of(l.bias)[1] for l in lins], dtype=np.int64)
             # (value -> block caches are shared by every plan of this expert: a second plan -- another batch size, an
             # evaluation program -- does not start from empty tables)
-            shared = eng.__dict__.setdefault("_cond_lookup", {}).setdefault((eid, key), dict(raw_index={}, cat_maps={}, last=None))
+            shared = eng._cond_lookup.setdefault((eid, key), dict(raw_index={}, cat_maps={}, last=None))
             ent = dict(base=len(w_off), w_idx=w_idx, b_idx=b_idx, layer=layer if isinstance(layer, ConditionalLayer) else None,
                        raw_index=shared["raw_index"], cat_maps=shared["cat_maps"], shared=shared)
             if ent["layer"] is not None:
@@ -376,7 +376,7 @@ class CondProgram:
             if absent_here is not None:
                 # segments that stepped last time and do not now: zeroed once (the dense all-reduce of the arena would
                 # otherwise sum their stale values on every step), skipped by the norm / Adam job kernels
-                prev = getattr(self.eng, "_cond_prev_union", None)  # engine-wide: every plan steps the same VAE arena
+                prev = self.eng._cond_prev_union  # engine-wide: every plan steps the same VAE arena
                 carry = np.empty(0, dtype=np.int64)
                 if prev is not None:
                     retired = np.setdiff1d(prev, act)

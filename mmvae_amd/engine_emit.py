@@ -101,16 +101,21 @@ class PlanEmit:
         the GEMM stays on the pipelined whole-k-tile kernel for any batch size."""
         return (rows + 31) // 32 * 32
 
-    def _plan_gemm(self, layout, M, N, K):
+    def _plan_tile(self, layout, M, N, K):
+        """(tile class, split-K count) the library's planner picks for this GEMM."""
         tile, sk = C.c_int(0), C.c_int(0)
         self.lib.mmvae_gemm_plan(layout, M, N, K, C.byref(tile), C.byref(sk))
-        return sk.value
+        return tile.value, sk.value
+
+    def _plan_gemm(self, layout, M, N, K):
+        return self._plan_tile(layout, M, N, K)[1]
 
     def _fuse_sqnorm(self, layout, M, N, K, alpha, A, lda, Bm, ldb, Cm, ldc, bias, flags, side_cap: int = 0,
-                     on_side: bool = True, planes=None, fork: bool = True, stream=None) -> bool:
+                     on_side: bool = True, planes=None, stream=None) -> bool:
         """Unsplit weight-gradient GEMM straight into a gradient arena: let its epilogue also leave the partial sums of
         squares of what it stores (mmvae_gemm_f32_sq), so that the clip's norm pass does not read the 82 MB back.  Only
-        without a gradient exchange: under data parallelism the norm is that of the REDUCED gradients."""
+        without a gradient exchange: under data parallelism the norm is that of the REDUCED gradients.  side_cap: capped
+        to that many workgroups, on the branch `stream` (default the side stream) unless on_side=False."""
         eng = self.eng
         if eng.overlap or eng.world > 1 or ldc != N or (flags & ~ACC):
             return False
@@ -132,85 +137,64 @@ class PlanEmit:
             return False
         self._sq_used[id(opt)] = base + n_part
         self._sq_cover.setdefault(id(opt), []).append((off, M * N))
-        plan = self
-
-        ap, bp = (planes[0].args() if planes and planes[0] else _NOPL), (planes[1].args() if planes and planes[1] else _NOPL)
-        tag, self._probe_next = self._probe_next, None
-
-        def launch_gemm():
-            if planes:
-                rc = plan.lib.mmvae_gemm_planes_f32(layout, M, N, K, alpha, _p(A), lda, *ap, _p(Bm), ldb, *bp, _p(Cm), ldc,
-                                                    _p(bias), flags | SLACK, 1, None, 0, buf.data_ptr() + 4 * base, n_part,
-                                                    _s())
-            else:
-                rc = plan.lib.mmvae_gemm_f32_sq(layout, M, N, K, alpha, _p(A), lda, _p(Bm), ldb, _p(Cm), ldc, _p(bias),
-                                                flags | SLACK, buf.data_ptr() + 4 * base, n_part, _s())
-            if rc != 0:
-                raise _lib.HipLibraryError(f"mmvae_gemm_f32_sq failed with code {rc} (layout {layout}, {M}x{N}x{K})")
-
-        launch = self._probed(tag, 2.0 * M * N * K, launch_gemm, bound="mfma", cus=side_cap, planes=_planes_desc(planes),
-                              shape=f"{('NT', 'NN', 'TN')[layout]} {M}x{N}x{K}")
-
-        if side_cap:  # persistent grid capped to `side_cap` workgroups: the CUs left over serve another branch
-            side = (stream if stream is not None else eng.side_stream) if on_side else None
-            if on_side and fork:
-                self._fork(side)
-
-            def call():
-                plan.lib.mmvae_gemm_set_workgroup_cap(side_cap)
-                try:
-                    if side is not None:
-                        with torch.cuda.stream(side):
-                            launch()
-                    else:
-                        launch()
-                finally:
-                    plan.lib.mmvae_gemm_set_workgroup_cap(0)
-        else:
-            call = launch
-        self._cur.append(call)
+        side = (stream if stream is not None else eng.side_stream) if on_side else None
+        self._gemm_launch(layout, M, N, K, alpha, A, lda, Bm, ldb, Cm, ldc, bias, flags, planes=planes,
+                          sq=(buf.data_ptr() + 4 * base, n_part), cap=side_cap, stream=side)
         return True
 
-    def _side_capped_gemm(self, layout, M, N, K, A, lda, Bm, ldb, Cm, ldc, cap: int, planes=None, flags: int = 0,
-                          sk: int = 1, fork: bool = True, stream=None) -> None:
-        """Unsplit GEMM on the side stream with its persistent grid capped to `cap` workgroups (no fused norm partials:
-        under a gradient exchange the clip's norm is that of the REDUCED gradients); joined by the next cut / _join()."""
-        plan = self
+    def _gemm_launch(self, layout, M, N, K, alpha, A, lda, Bm, ldb, Cm, ldc, bias, flags, sk: int = 1, planes=None,
+                     use_ws: bool = False, sq=None, cap: int = 0, stream=None) -> None:
+        """Emit one GEMM launch.  planes: (A planes or None, B planes or None) -- pre-split forms of the operands
+        (_PlaneBuf); the fp32 pointers stay the library's fallback for shapes the planes kernels do not take.  Cm None:
+        the shared slab buffer; use_ws: the shared split-K workspace; sq: (pointer, count) of the norm-partial slots its
+        epilogue fills (mmvae_gemm_f32_sq).  cap: the persistent grid capped to `cap` workgroups -- the CUs left over serve
+        another branch -- on branch `stream` (None: the current stream), forked from the main stream first; joined by the
+        next cut / _join()."""
+        plan, lib = self, self.lib
         ap, bp = (planes[0].args() if planes and planes[0] else _NOPL), (planes[1].args() if planes and planes[1] else _NOPL)
         tag, self._probe_next = self._probe_next, None
+        sq_args = sq if sq else (None, 0)
 
         def launch_gemm():
+            ws = (plan.ws.data_ptr(), plan.ws.numel() * 4) if use_ws else (None, 0)
+            c_ptr = _p(Cm) if Cm is not None else plan.slab.data_ptr()
             if planes:
-                rc = plan.lib.mmvae_gemm_planes_f32(layout, M, N, K, 1.0, _p(A), lda, *ap, _p(Bm), ldb, *bp, _p(Cm), ldc,
-                                                    None, flags | SLACK, sk, None, 0, None, 0, _s())
+                rc = lib.mmvae_gemm_planes_f32(layout, M, N, K, alpha, _p(A), lda, *ap, _p(Bm), ldb, *bp, c_ptr, ldc,
+                                               _p(bias), flags | SLACK, sk, *ws, *sq_args, _s())
+            elif sq:
+                rc = lib.mmvae_gemm_f32_sq(layout, M, N, K, alpha, _p(A), lda, _p(Bm), ldb, c_ptr, ldc, _p(bias),
+                                           flags | SLACK, *sq, _s())
             else:
-                rc = plan.lib.mmvae_gemm_f32(layout, M, N, K, 1.0, _p(A), lda, _p(Bm), ldb, _p(Cm), ldc, None,
-                                             flags | SLACK, sk, None, 0, _s())
+                rc = lib.mmvae_gemm_f32(layout, M, N, K, alpha, _p(A), lda, _p(Bm), ldb, c_ptr, ldc, _p(bias),
+                                        flags | SLACK, sk, *ws, _s())
             if rc != 0:
-                raise _lib.HipLibraryError(f"capped side GEMM failed with code {rc} (layout {layout}, {M}x{N}x{K})")
+                raise _lib.HipLibraryError(f"GEMM launch failed with code {rc} (layout {layout}, {M}x{N}x{K})")
 
         launch = self._probed(tag, 2.0 * M * N * K, launch_gemm, bound="mfma", cus=cap, planes=_planes_desc(planes),
                               shape=f"{('NT', 'NN', 'TN')[layout]} {M}x{N}x{K}" + (f" split-K {sk}" if sk > 1 else ""))
-        side = stream if stream is not None else self.eng.side_stream
-        if fork:
-            self._fork(side)
+        if not cap:
+            self._cur.append(launch)
+            return
+        if stream is not None:
+            self._fork(stream)
 
         def call():
-            plan.lib.mmvae_gemm_set_workgroup_cap(cap)
+            lib.mmvae_gemm_set_workgroup_cap(cap)
             try:
-                with torch.cuda.stream(side):
+                if stream is not None:
+                    with torch.cuda.stream(stream):
+                        launch()
+                else:
                     launch()
             finally:
-                plan.lib.mmvae_gemm_set_workgroup_cap(0)
+                lib.mmvae_gemm_set_workgroup_cap(0)
 
         self._cur.append(call)
 
     def _queue_gemm(self, layout, M, N, K, alpha, A, lda, Bm, ldb, Cm, ldc, bias, flags) -> bool:
         """Weight-gradient GEMMs of the core layers (the planner's 64x64-tile class) are independent of each other and
         only feed the optimiser: queue them for ONE grouped launch (_flush_gemms) instead of a launch each."""
-        tile, sk = C.c_int(0), C.c_int(0)
-        self.lib.mmvae_gemm_plan(layout, M, N, K, C.byref(tile), C.byref(sk))
-        if tile.value != 2:
+        if self._plan_tile(layout, M, N, K)[0] != 2:
             return False
         job = _lib.GemmJob(_p(A), _p(Bm), _p(Cm), _p(bias), lda, ldb, ldc, layout, M, N, K, float(alpha), int(flags), 0, 0)
         if not self.lib.mmvae_gemm_batch_job_ok(C.addressof(job)):
@@ -246,32 +230,33 @@ class PlanEmit:
         (nothing emitted) when a job is not of that class."""
         arr = []
         for layout, M, N, K, A, lda, Bm, ldb, Cm, ldc, bias, flags, alpha in jobs:
-            tile, sk = C.c_int(0), C.c_int(0)
-            self.lib.mmvae_gemm_plan(layout, M, N, K, C.byref(tile), C.byref(sk))
+            tile = self._plan_tile(layout, M, N, K)[0]
             job = _lib.GemmJob(_p(A), _p(Bm), _p(Cm), _p(bias), lda, ldb, ldc, layout, M, N, K, float(alpha), int(flags), 0, 0)
-            if tile.value != 2 or not self.lib.mmvae_gemm_batch_job_ok(C.addressof(job)):
+            if tile != 2 or not self.lib.mmvae_gemm_batch_job_ok(C.addressof(job)):
                 return False
             arr.append(job)
             self._sum_keep.append((A, Bm, Cm, bias))
-        table = (_lib.GemmJob * len(arr))(*arr)
-        total = C.c_int(0)
-        _lib.check(self.lib.mmvae_gemm_batch_prepare(len(arr), C.addressof(table), C.byref(total)), "mmvae_gemm_batch_prepare")
-        jobs_dev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(self.eng.device)
-        self._job_tables.append(jobs_dev)
-        self._emit(self.lib.mmvae_gemm_batch_f32, len(arr), jobs_dev.data_ptr(), total.value)
+        self._emit_gemm_batch(arr)
         return True
 
     def _flush_gemms(self):
-        if not self._gemm_jobs:
-            return
-        n = len(self._gemm_jobs)
-        arr = (_lib.GemmJob * n)(*self._gemm_jobs)
+        if self._gemm_jobs:
+            self._emit_gemm_batch(self._gemm_jobs)
+            self._gemm_jobs = []
+
+    def _emit_gemm_batch(self, jobs):
+        """One mmvae_gemm_batch_f32 launch over `jobs` (GemmJob)."""
+        table = (_lib.GemmJob * len(jobs))(*jobs)
         total = C.c_int(0)
-        _lib.check(self.lib.mmvae_gemm_batch_prepare(n, C.addressof(arr), C.byref(total)), "mmvae_gemm_batch_prepare")
-        jobs_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.eng.device)
-        self._job_tables.append(jobs_dev)
-        self._emit(self.lib.mmvae_gemm_batch_f32, n, jobs_dev.data_ptr(), total.value)
-        self._gemm_jobs = []
+        _lib.check(self.lib.mmvae_gemm_batch_prepare(len(jobs), C.addressof(table), C.byref(total)), "mmvae_gemm_batch_prepare")
+        self._emit(self.lib.mmvae_gemm_batch_f32, len(jobs), self._upload_table(table), total.value)
+
+    def _upload_table(self, table) -> int:
+        """A host job table (ctypes array) in device memory that lives as long as the plan (the captured graph reads it on
+        every replay); returns its device pointer."""
+        t = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(self.eng.device)
+        self._job_tables.append(t)
+        return t.data_ptr()
 
     def gemm(self, layout, M, N, K, A, lda, Bm, ldb, Cm, ldc, bias=None, flags=0, alpha=1.0, side=False, planes=None):
         """Complete GEMM (internal split-K reduce through a workspace when the plan asks for it).  side=True runs it
@@ -284,14 +269,14 @@ class PlanEmit:
             # pending reduction of the backward pass in ONE mmvae_sum_parts_batch launch (a reduce launch per GEMM is
             # ~5 us of pure launch cost)
             slabs = self.eng.buf(f"dwslabs.{self._next_defer_id()}", (sk, M, N))
-            self._emit_gemm(layout, M, N, K, 1.0, A, lda, Bm, ldb, slabs, N, None, RAW, sk, False, planes=planes)
+            self._gemm_launch(layout, M, N, K, 1.0, A, lda, Bm, ldb, slabs, N, None, RAW, sk=sk, planes=planes)
             self._defer_sum(slabs, sk, M * N, M, N, N, Cm, ldc, alpha, flags & ACC)
             return
         if side and sk == 1 and self._fuse_sqnorm(layout, M, N, K, alpha, A, lda, Bm, ldb, Cm, ldc, bias, flags, planes=planes):
             return
         nbytes = self.lib.mmvae_gemm_workspace_bytes(layout, M, N, K, sk)
         self._ws_bytes = max(self._ws_bytes, nbytes)
-        self._emit_gemm(layout, M, N, K, alpha, A, lda, Bm, ldb, Cm, ldc, bias, flags, sk, True, planes=planes)
+        self._gemm_launch(layout, M, N, K, alpha, A, lda, Bm, ldb, Cm, ldc, bias, flags, sk=sk, planes=planes, use_ws=True)
 
     def _edge(self, src, dst):
         """dst waits for everything enqueued so far on src (None = the current stream at run time): a graph edge under
@@ -312,13 +297,12 @@ class PlanEmit:
     def _next_x_split_job(self, l: _LayerRef, rows: int):
         """The next piece of the input batch's split for a layer whose tail is a column-kernel launch (fwd_layer's slab
         path), or None."""
-        jobs = getattr(self, "_x_split_jobs", None)
-        if not jobs:
+        if not self._x_split_jobs:
             return None
         p_drop = l.p if self.mode == "train" else 0.0
         if l.bn is None and p_drop == 0 and self._plan_gemm(NT, rows, l.n_out, l.n_in) == 1:
             return None  # this layer's tail is fused into its GEMM
-        return jobs.pop(0)
+        return self._x_split_jobs.pop(0)
 
     def _fork(self, stream=None):
         """A branch stream (default: the side stream) waits for everything enqueued so far on the main stream."""
@@ -361,7 +345,7 @@ class PlanEmit:
 
     def _next_defer_id(self) -> int:
         # position in this plan's program: the same geometry built again (another input pointer) shares the buffers
-        self._defer_id = getattr(self, "_defer_id", 0) + 1
+        self._defer_id += 1
         return self._defer_id
 
     def _defer_sum(self, src, n_parts, part_stride, rows, cols, ld_src, dst, ld_dst, alpha=1.0, flags=0):
@@ -376,9 +360,7 @@ class PlanEmit:
         if not self._sum_jobs:
             return
         arr = (_lib.SumJob * len(self._sum_jobs))(*self._sum_jobs)
-        jobs_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.eng.device)
-        self._job_tables.append(jobs_dev)  # lives as long as the plan (the captured graph reads it on every replay)
-        self._emit(self.lib.mmvae_sum_parts_batch, len(self._sum_jobs), jobs_dev.data_ptr(),
+        self._emit(self.lib.mmvae_sum_parts_batch, len(self._sum_jobs), self._upload_table(arr),
                    max(int(j.rows) * int(j.cols) for j in self._sum_jobs))
         self._sum_jobs = []
 
@@ -386,35 +368,8 @@ class PlanEmit:
         """Raw split-K slabs into the shared slab buffer; returns the slab count."""
         sk = self._plan_gemm(layout, M, N, K)
         self._slab_floats = max(self._slab_floats, sk * M * N)
-        self._emit_gemm(layout, M, N, K, 1.0, A, lda, Bm, ldb, None, N, None, RAW, sk, False, planes=planes)
+        self._gemm_launch(layout, M, N, K, 1.0, A, lda, Bm, ldb, None, N, None, RAW, sk=sk, planes=planes)
         return sk
-
-    def _emit_gemm(self, layout, M, N, K, alpha, A, lda, Bm, ldb, Cm, ldc, bias, flags, sk, use_ws, planes=None):
-        """planes: (A planes or None, B planes or None) -- pre-split forms of the operands (_PlaneBuf); the fp32 pointers
-        stay the library's fallback for shapes the planes kernels do not take."""
-        plan = self
-        tag, self._probe_next = self._probe_next, None
-        ap, bp = (planes[0].args() if planes and planes[0] else _NOPL), (planes[1].args() if planes and planes[1] else _NOPL)
-
-        def launch_gemm():
-            ws = plan.ws
-            c_ptr = _p(Cm) if Cm is not None else plan.slab.data_ptr()
-            if planes:
-                rc = plan.lib.mmvae_gemm_planes_f32(layout, M, N, K, alpha, _p(A), lda, *ap, _p(Bm), ldb, *bp, c_ptr, ldc,
-                                                    _p(bias), flags | SLACK, sk, ws.data_ptr() if use_ws else None,
-                                                    ws.numel() * 4 if use_ws else 0, None, 0, _s())
-            else:
-                rc = plan.lib.mmvae_gemm_f32(layout, M, N, K, alpha, _p(A), lda, _p(Bm), ldb, c_ptr, ldc, _p(bias),
-                                             flags | SLACK, sk, ws.data_ptr() if use_ws else None,
-                                             ws.numel() * 4 if use_ws else 0, _s())
-            if rc != 0:
-                raise _lib.HipLibraryError(f"mmvae_gemm_f32 failed with code {rc} (layout {layout}, {M}x{N}x{K})")
-
-        launch = self._probed(tag, 2.0 * M * N * K, launch_gemm, bound="mfma", cus=0, planes=_planes_desc(planes),
-                              shape=f"{('NT', 'NN', 'TN')[layout]} {M}x{N}x{K}" + (f" split-K {sk}" if sk > 1 else ""))
-
-        call = launch
-        self._cur.append(call)
 
     # ---- one FCBlock layer forward: cur [rows, n_in] -> l.d
     def fwd_layer(self, tag: str, l: _LayerRef, cur: torch.Tensor, ld_cur: int, rows: int, training: bool = True,
@@ -436,7 +391,7 @@ class PlanEmit:
         l.a = eng.buf(f"{tag}.a", (rows, l.n_out)) if (l.p > 0 and l.return_hidden and training) else None
         l.dz = eng.buf(f"{tag}.dz", (rows, l.n_out)) if training else None
         p_drop = l.p if training else 0.0
-        self._fcws_bytes = max(getattr(self, "_fcws_bytes", 0), self.lib.mmvae_fc_workspace_bytes(rows, l.n_out))
+        self._fcws_bytes = max(self._fcws_bytes, self.lib.mmvae_fc_workspace_bytes(rows, l.n_out))
         sk = self._plan_gemm(NT, rows, l.n_out, l.n_in)
         if l.bn is None and p_drop == 0 and sk == 1:
             self.gemm(NT, rows, l.n_out, l.n_in, cur, ld_cur, l.W, l.n_in, l.d, l.n_out, bias=l.b,
@@ -482,8 +437,7 @@ class PlanEmit:
         its input -- both operands of its weight-gradient GEMM.  row_scale: per-row factor of the incoming gradient
         (the K-sample bound's weights, applied where the slabs are summed)."""
         rows = l.rows
-        dw_planes = (dz_planes, inp_planes) if (dz_planes is not None and (inp_planes is not None or
-                                                                         getattr(self, "x_fp32_dw1", False))) else None
+        dw_planes = (dz_planes, inp_planes) if (dz_planes is not None and (inp_planes is not None or self.x_fp32_dw1)) else None
         plan = self
         relu_src = l.a if l.a is not None else l.d
         has_bn = l.bn is not None
@@ -511,11 +465,10 @@ class PlanEmit:
         # dW[n_out, n_in] = dz^T[n_out, rows] . inp[rows, n_in]  -> straight into the gradient arena
         # (an adversary reading the first of K > 1 samples: the rows behind its B input rows are the next sample, not slack)
         k_rows = rows if (self.K > 1 and l.inp is self.z and rows != self.R) else self.kpad(rows)
-        if getattr(self, "_defer_next_dw", False):
+        if self._defer_next_dw:
             # (side-branch mode) the first layer's chip-filling weight gradient is emitted behind the shared VAE's
             # optimiser: by then the decoder's weight gradient on the side branch has released its CUs
-            self._deferred_dw = (TN, l.n_out, l.n_in, k_rows, l.dz, l.n_out, l.inp, l.ld_inp, l.gW, l.n_in)
-            self._deferred_dw_planes = dw_planes
+            self._deferred_dw = ((TN, l.n_out, l.n_in, k_rows, l.dz, l.n_out, l.inp, l.ld_inp, l.gW, l.n_in), dw_planes)
             self._defer_next_dw = False
         else:
             big_first = l is self.enc_layers[0] and 2.0 * l.n_out * l.n_in * k_rows >= 5e9
@@ -546,7 +499,7 @@ class PlanEmit:
         plan = self
         rows = 2 * B
         RC = rows // 32
-        self._fcws_bytes = max(getattr(self, "_fcws_bytes", 0), self.lib.mmvae_fc_workspace_bytes(rows, N))
+        self._fcws_bytes = max(self._fcws_bytes, self.lib.mmvae_fc_workspace_bytes(rows, N))
         ws = self.eng.buf(f"biasparts.{self._next_defer_id()}",
                           (max(self.lib.mmvae_fc_workspace_bytes(rows, N) // 4, RC * N),))
         self._defer_sum(ws, RC // 2, N, 1, N, N, dbias0, N)
@@ -564,7 +517,7 @@ class PlanEmit:
     def _emit_fc_bwd(self, rows, N, din, addend, row_scale, dz_out, dbias):
         """Plain (no BN / ReLU / mask) column pass: dz = row_scale * (din + addend) (optional), dbias = column sums."""
         plan = self
-        self._fcws_bytes = max(getattr(self, "_fcws_bytes", 0), self.lib.mmvae_fc_workspace_bytes(rows, N))
+        self._fcws_bytes = max(self._fcws_bytes, self.lib.mmvae_fc_workspace_bytes(rows, N))
         own_ws = self._bias_partials(rows, N, dbias) if dbias is not None else None
 
         def call():

@@ -192,10 +192,9 @@ class PlanRun:
         sync).  The views and tagged dictionaries are built once per (stage, expert): ~25 tensor views per step were a
         tenth of the host's share of an adversarial step."""
         key = (model.stage_name, eid)
-        cache = self.__dict__.setdefault("_log_cache", {})
-        calls = cache.get(key)
+        calls = self._log_cache.get(key)
         if calls is None:
-            calls = cache[key] = self._log_calls(model, eid)
+            calls = self._log_cache[key] = self._log_calls(model, eid)
         for kind, a, b in calls:
             if kind == "auto":
                 model.auto_log(a, **b)
@@ -208,7 +207,7 @@ class PlanRun:
         calls = []
         main = {RK.LOSS: m[self.slot("total_loss")], RK.RECON_LOSS: m[1], RK.KL_LOSS: m[2], RK.KL_WEIGHT: m[3],
                 "Mean": m[4], "Variance": m[5]}
-        for i in range(1, getattr(self, "n_adv", 0) + 1):
+        for i in range(1, self.n_adv + 1):
             for phase in ("discriminator", "generator"):
                 tags = [f"{phase}_{i}", stage, eid, RK.ADV_LOSS]
                 for c in self.conditions + ["summed"]:

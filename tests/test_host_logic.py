@@ -329,6 +329,60 @@ def test_forked_programs_are_fenced_to_validated_runtimes():
     assert forks_allowed(dataclasses.replace(st, side_dw_any=True), "7.2.26015")
 
 
+# (B, K, G, adversaries, conditional layers, exchange, validated runtime, MMVAE_SIDE_DW_ANY) -> (side_dw, early, late,
+# adv_aside, adv_dw2, adv_lane, dp_dw, prefetch, prefetch cap, prefetch on the second branch)
+_LAYOUTS = {
+    "C1": ((128, 1, 2000, False, False, False, True, False), (0, False, False, False, False, False, 0, False, 0, False)),
+    "C2": ((512, 1, 20000, False, False, False, True, False), (125, True, True, False, False, False, 0, True, 128, False)),
+    "C3": ((512, 10, 20000, False, False, False, True, False), (0, False, False, False, False, False, 0, False, 0, False)),
+    "C4": ((512, 1, 20000, True, False, False, True, False), (0, False, True, True, True, False, 0, True, 86, True)),
+    "C5": ((1024, 5, 30000, False, False, False, True, False), (0, False, False, False, False, False, 0, False, 0, False)),
+    "60530 genes": ((512, 1, 60530, False, False, False, True, False),
+                    (0, False, False, False, False, False, 0, False, 0, False)),
+    "52437 genes": ((512, 1, 52437, False, False, False, True, False),
+                    (0, False, False, False, False, False, 0, False, 0, False)),
+    "8000 genes": ((512, 1, 8000, False, False, False, True, False), (0, False, False, False, False, False, 0, False, 0, False)),
+    "8000 genes, any geometry": ((512, 1, 8000, False, False, False, True, True),
+                                 (125, True, True, False, False, False, 0, True, 128, False)),
+    "conditional": ((512, 1, 20000, False, True, False, True, False),
+                    (125, True, True, False, False, False, 0, True, 128, False)),
+    "C2 exchange": ((512, 1, 20000, False, False, True, True, False), (0, False, False, False, False, False, 125, False, 0, False)),
+    "C4 exchange": ((512, 1, 20000, True, False, True, True, False), (0, False, False, False, False, True, 0, False, 0, False)),
+    "C2, runtime not validated": ((512, 1, 20000, False, False, False, False, False),
+                                  (0, False, False, False, False, False, 0, False, 0, False)),
+}
+
+
+@pytest.mark.parametrize("case", list(_LAYOUTS))
+def test_plan_layout_places_the_branches_of_the_measured_geometry(case):
+    """Which branch streams a training program forks onto, per configuration (one rank, the default settings, a 1024-wide
+    last hidden layer): the forked programs are those of C2's geometry and of C4's; every other shape stays on one stream
+    unless MMVAE_SIDE_DW_ANY=1.  The engine facts follow the settings as StepEngine sets them up."""
+    import dataclasses
+
+    from mmvae_amd.engine import EngineSettings, plan_layout
+
+    (B, K, G, adv, cond, exchange, validated, any_geometry), want = _LAYOUTS[case]
+    st = dataclasses.replace(EngineSettings(), side_dw_any=any_geometry)
+    fork_ok = validated or any_geometry  # (forks_allowed)
+    side_dw = st.side_dw if fork_ok else 0
+    side_dw_dp = st.side_dw_dp if fork_ok else 0
+    L = plan_layout(st, fork_ok=fork_ok, side_stream=bool(side_dw or side_dw_dp),
+                    side_stream2=bool(side_dw and st.adv_aside >= 2 and st.adv_fused), lane_stream=exchange,
+                    overlap=exchange, world=1, mode="train", B=B, K=K, R=B * K, G=G, n_in_last=1024, iwae=False,
+                    has_adv=adv, has_cond=cond, adv_reducer=False)
+    got = (L.side_dw, L.early, L.late, L.adv_aside, L.adv_dw2, L.adv_lane, L.dp_dw, L.prefetch,
+           L.prefetch_cap if L.prefetch else 0, L.prefetch_side2 if L.prefetch else False)
+    assert got == want
+    if L.late:
+        assert L.late_cap == st.side_dw2
+    # forward-only programs never fork
+    ev = plan_layout(st, fork_ok=True, side_stream=True, side_stream2=True, lane_stream=True, overlap=exchange, world=1,
+                     mode="validate", B=B, K=K, R=B * K, G=G, n_in_last=1024, iwae=False, has_adv=adv, has_cond=cond,
+                     adv_reducer=False)
+    assert not (ev.side_dw or ev.late or ev.adv_aside or ev.adv_lane or ev.dp_dw or ev.prefetch)
+
+
 def test_lookahead_announces_the_next_batch_and_the_model_consumes_the_hint():
     """mmvae_amd.trainer.Lookahead (the loop side of the step engine's software pipelining across steps): batches come out
     in order and unchanged, and before each one the model is told which one follows (None behind the last)."""
