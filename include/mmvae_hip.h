@@ -40,7 +40,7 @@ typedef void* mmvae_stream_t; /* hipStream_t */
 /* ABI version: bumped whenever an entry point is added or a signature changes (mmvae_abi_version() returns the
  * value the library was built with; bindings compare it with the header they were written against).
  *   1  round-1 surface (first 20 entry points)      2  end of round 1 (50 entry points)      3+  round 2 */
-#define MMVAE_ABI_VERSION 10
+#define MMVAE_ABI_VERSION 11
 int mmvae_abi_version(void);
 const char* mmvae_build_arch(void);
 
@@ -202,6 +202,36 @@ int mmvae_layernorm_fwd(int B, int N, const float* x, int64_t ldx, float eps, fl
                         float* save_invstd, mmvae_stream_t stream);
 int mmvae_layernorm_bwd(int B, int N, const float* dy, int64_t lddy, const float* y, int64_t ldy,
                         const float* save_invstd, float* dx, int64_t lddx, mmvae_stream_t stream);
+
+/* Fused row tail of an FCBlock layer WITH LayerNorm: Linear -> [BatchNorm] -> LayerNorm(no affine) -> [ReLU] -> [Dropout]
+ * (components.py:275-290; configs/model/configV3.yaml builds the shared VAE's encoder this way).  One wavefront per row,
+ * one launch each way where slab sum + bias, mmvae_layernorm_fwd/bwd and the ReLU / dropout tail were three.
+ *   v = bias + sum_s in[s]   (slab order)        y = (v - mean_row(v)) / sqrt(var_row(v) + eps)   (biased variance, fp32
+ *   a = relu ? max(y, 0) : y                     d = mask ? a * mask / (1 - p) : a                 two-pass statistics)
+ * y_out (the normalised row), a_out (the activation before dropout) and save_invstd [B] are what the backward pass reads;
+ * each of y_out / a_out may be NULL when another output holds the same values (no ReLU and no mask: y = a = d; no mask:
+ * a = d).  training = 0 (eval mode): keep_mask must be NULL and nothing but d_out is written.  Any N: rows up to 1024
+ * wide stay in registers, wider ones are read three times.  A layer with BatchNorm runs mmvae_fc_epilogue_fwd first (no
+ * ReLU, no mask) and this tail over its output with n_slabs = 1 and bias = NULL. */
+int mmvae_fc_rowtail_fwd(int B, int N, const float* in, int64_t ld_in, int n_slabs, const float* bias /* or NULL */,
+                         float eps, int training, int relu, const uint8_t* keep_mask /* [B,N] or NULL */, float dropout_p,
+                         float* y_out, float* a_out, float* d_out, int64_t ld_out, float* save_invstd,
+                         mmvae_stream_t stream);
+
+/* Backward of the same tail.
+ *   g  = row_scale[b] * sum_s din[s]                       (row_scale optional: the K-sample weights of the incoming
+ *                                                           gradient, as in mmvae_fc_epilogue_bwd)
+ *   g  = (mask ? g * mask / (1 - p) : g) + addend          (addend: optional gradient on the hidden representation = the
+ *                                                           activation before dropout; it bypasses the keep mask)
+ *   g  = relu ? g * 1[act > 0] : g                         (act: forward a_out, or d_out without dropout)
+ *   dz = save_invstd[b] * (g - mean_row(g) - y * mean_row(g * y))
+ * A non-NULL workspace ([ceil(B/32)][N] floats) receives the per-32-row-chunk column sums of dz (fixed order, no atomics:
+ * bitwise reproducible); they are summed into dbias when dbias is non-NULL, otherwise the caller finishes them, e.g. in
+ * its mmvae_sum_parts_batch launch.  workspace = NULL: no bias gradient (the layer's Linear feeds a BatchNorm). */
+int mmvae_fc_rowtail_bwd(int B, int N, const float* din, int64_t ld_in, int n_slabs, const float* addend,
+                         const float* row_scale, const uint8_t* keep_mask, float dropout_p, int relu, const float* act,
+                         const float* y, const float* save_invstd, float* dz_out, int64_t ld_out, float* dbias,
+                         float* workspace, size_t workspace_bytes, mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Reparameterisation + Gaussian KL (k8)

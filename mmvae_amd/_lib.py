@@ -79,6 +79,8 @@ PROTOTYPES = {
     ),
     "mmvae_layernorm_fwd": (_i, [_i, _i, _p, _l, _f, _p, _l, _p, _p, _p]),
     "mmvae_layernorm_bwd": (_i, [_i, _i, _p, _l, _p, _l, _p, _p, _l, _p]),
+    "mmvae_fc_rowtail_fwd": (_i, [_i, _i, _p, _l, _i, _p, _f, _i, _i, _p, _f, _p, _p, _p, _l, _p, _p]),
+    "mmvae_fc_rowtail_bwd": (_i, [_i, _i, _p, _l, _i, _p, _p, _p, _f, _i, _p, _p, _p, _p, _l, _p, _p, _z, _p]),
     "mmvae_reparam_kl_fwd": (_i, [_i, _i, _i, _p, _p, _p, _f, _p, _p, _p, _p, _p]),
     "mmvae_reparam_kl_bwd": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p]),
     "mmvae_mse_sum_fwd_bwd": (_i, [_i, _i, _p, _l, _p, _l, _p, _p, _l, _p, _f, _p]),

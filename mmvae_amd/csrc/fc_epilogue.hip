@@ -485,6 +485,198 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(int B, int N, const 
     for (int j = lane; j < N; j += 64) dr[j] = invstd * (gr[j] - m1 - yr[j] * m2);
 }
 
+// ---- Fused row tail of a LayerNorm layer (Linear -> [BatchNorm] -> LayerNorm(no affine) -> [ReLU] -> [Dropout]) ----
+// One wavefront per row, the row in registers: lane l holds the NV columns l, l + 64, ... (every access one coalesced
+// 256-B wave access; any N <= 64 * NV, odd ones included).  Forward: split-K slabs + bias -> two-pass row statistics
+// -> ReLU -> keep mask, one launch where slab sum, mmvae_layernorm_fwd and the ReLU / dropout tail were three.
+struct RowFwdArgs {
+    const float* in;
+    int64_t ld_in, slab_stride;
+    int n_slabs;
+    const float* bias;
+    float eps;
+    int relu;
+    const uint8_t* mask;
+    float keep_scale;
+    float* y_out;
+    float* a_out;
+    float* d_out;
+    int64_t ld_out;
+    float* save_invstd;
+    int B, N;
+};
+
+__device__ __forceinline__ void rowtail_store(const RowFwdArgs& a, int row, int c, float y) {
+    const int64_t o = (int64_t)row * a.ld_out + c;
+    if (a.y_out) a.y_out[o] = y;
+    const float act = a.relu ? fmaxf(y, 0.f) : y;
+    if (a.a_out) a.a_out[o] = act;
+    a.d_out[o] = a.mask ? (a.mask[(int64_t)row * a.N + c] ? act * a.keep_scale : 0.f) : act;
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void fc_rowtail_fwd_kernel(const RowFwdArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= a.B) return;  // (wave-uniform)
+    const float* xr = a.in + (int64_t)row * a.ld_in;
+    float v[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const int c = lane + 64 * k;
+        v[k] = (c < a.N && a.bias) ? a.bias[c] : 0.f;
+    }
+    for (int s = 0; s < a.n_slabs; ++s) {  // slab order: bitwise the column kernels' sum
+        const float* xs = xr + (int64_t)s * a.slab_stride;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            const int c = lane + 64 * k;
+            if (c < a.N) v[k] += xs[c];
+        }
+    }
+    float s1 = 0.f;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) s1 += v[k];  // (columns >= N hold zeros)
+    const float mean = wave_sum(s1) / (float)a.N;
+    float s2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        v[k] = (lane + 64 * k < a.N) ? v[k] - mean : 0.f;
+        s2 += v[k] * v[k];
+    }
+    const float invstd = 1.0f / sqrtf(wave_sum(s2) / (float)a.N + a.eps);
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const int c = lane + 64 * k;
+        if (c < a.N) rowtail_store(a, row, c, v[k] * invstd);
+    }
+    if (lane == 0 && a.save_invstd) a.save_invstd[row] = invstd;
+}
+
+// Any width: the row is read three times (the second and third time from cache), d_out holds the summed row in between.
+__global__ __launch_bounds__(256) void fc_rowtail_fwd_loop_kernel(const RowFwdArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= a.B) return;
+    const float* xr = a.in + (int64_t)row * a.ld_in;
+    float* dr = a.d_out + (int64_t)row * a.ld_out;
+    float s1 = 0.f;
+    for (int c = lane; c < a.N; c += 64) {
+        float v = a.bias ? a.bias[c] : 0.f;
+        for (int s = 0; s < a.n_slabs; ++s) v += xr[(int64_t)s * a.slab_stride + c];
+        dr[c] = v;  // (read back by the lane that wrote it)
+        s1 += v;
+    }
+    const float mean = wave_sum(s1) / (float)a.N;
+    float s2 = 0.f;
+    for (int c = lane; c < a.N; c += 64) {
+        const float d = dr[c] - mean;
+        s2 += d * d;
+    }
+    const float invstd = 1.0f / sqrtf(wave_sum(s2) / (float)a.N + a.eps);
+    for (int c = lane; c < a.N; c += 64) rowtail_store(a, row, c, (dr[c] - mean) * invstd);
+    if (lane == 0 && a.save_invstd) a.save_invstd[row] = invstd;
+}
+
+struct RowBwdArgs {
+    const float* din;
+    int64_t ld_in, slab_stride;
+    int n_slabs;
+    const float* addend;     // gradient on the pre-dropout activation: added behind the keep mask
+    const float* row_scale;  // per-row factor of the incoming gradient
+    const uint8_t* mask;
+    float keep_scale;
+    int relu;
+    const float* act;  // forward a_out, or d_out without dropout: the ReLU slope is 1[act > 0]
+    const float* y;    // the normalised row
+    const float* save_invstd;
+    float* dz_out;
+    int64_t ld_out;
+    float* ws;  // [RC][N] per-chunk column sums of dz, or NULL
+    int B, N;
+};
+
+// The gradient at the LayerNorm's output for element (row, c): din through row_scale, dropout, addend and the ReLU.
+__device__ __forceinline__ float rowtail_dy(const RowBwdArgs& a, int row, int c, float rs) {
+    const float* gp = a.din + (int64_t)row * a.ld_in + c;
+    float g = 0.f;
+    for (int s = 0; s < a.n_slabs; ++s) g += gp[(int64_t)s * a.slab_stride];
+    const int64_t o = (int64_t)row * a.ld_out + c;
+    g *= rs;
+    if (a.mask) g = a.mask[(int64_t)row * a.N + c] ? g * a.keep_scale : 0.f;
+    if (a.addend) g += a.addend[o];
+    if (a.relu) g = (a.act[o] > 0.f) ? g : 0.f;
+    return g;
+}
+
+// Backward: a workgroup of four waves owns a 32-row chunk (8 rows per wave, one after the other); dz = invstd *
+// (g - mean(g) - y * mean(g * y)) per row, and the chunk's column sums of dz -- each wave's 8 rows in registers, the
+// four waves through LDS, fixed order: bitwise reproducible -- go to ws[chunk][N] for the deferred reduction.
+template <int NV>
+__global__ __launch_bounds__(256) void fc_rowtail_bwd_kernel(const RowBwdArgs a) {
+    __shared__ float red[4][64 * NV];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int chunk = blockIdx.x;
+    float col[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) col[k] = 0.f;
+#pragma unroll 2
+    for (int i = 0; i < RPW; ++i) {
+        const int row = chunk * RPC + w * RPW + i;
+        if (row >= a.B) break;  // (wave-uniform)
+        const float rs = a.row_scale ? a.row_scale[row] : 1.f;
+        float g[NV], yv[NV];
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            const int c = lane + 64 * k;
+            const bool cv = c < a.N;
+            g[k] = cv ? rowtail_dy(a, row, c, rs) : 0.f;
+            yv[k] = cv ? a.y[(int64_t)row * a.ld_out + c] : 0.f;
+            s1 += g[k];
+            s2 += g[k] * yv[k];
+        }
+        const float m1 = wave_sum(s1) / (float)a.N, m2 = wave_sum(s2) / (float)a.N;
+        const float invstd = a.save_invstd[row];
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            const int c = lane + 64 * k;
+            if (c < a.N) {
+                const float dz = invstd * (g[k] - m1 - yv[k] * m2);
+                a.dz_out[(int64_t)row * a.ld_out + c] = dz;
+                col[k] += dz;
+            }
+        }
+    }
+    if (!a.ws) return;  // (block-uniform)
+#pragma unroll
+    for (int k = 0; k < NV; ++k) red[w][lane + 64 * k] = col[k];
+    __syncthreads();
+    for (int c = threadIdx.x; c < a.N; c += 256)
+        a.ws[(int64_t)chunk * a.N + c] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+}
+
+// Any width: one wave per row, g parked in dz_out between the two passes; the column sums are a column pass of their own
+// (fc_bwd_stats_kernel over dz).
+__global__ __launch_bounds__(256) void fc_rowtail_bwd_loop_kernel(const RowBwdArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= a.B) return;
+    const float rs = a.row_scale ? a.row_scale[row] : 1.f;
+    const float* yr = a.y + (int64_t)row * a.ld_out;
+    float* dr = a.dz_out + (int64_t)row * a.ld_out;
+    float s1 = 0.f, s2 = 0.f;
+    for (int c = lane; c < a.N; c += 64) {
+        const float g = rowtail_dy(a, row, c, rs);
+        dr[c] = g;  // (read back by the lane that wrote it)
+        s1 += g;
+        s2 += g * yr[c];
+    }
+    const float m1 = wave_sum(s1) / (float)a.N, m2 = wave_sum(s2) / (float)a.N;
+    const float invstd = a.save_invstd[row];
+    for (int c = lane; c < a.N; c += 64) dr[c] = invstd * (dr[c] - m1 - yr[c] * m2);
+}
+
 }  // namespace
 
 extern "C" size_t mmvae_fc_workspace_bytes(int B, int N) {
@@ -699,5 +891,111 @@ extern "C" int mmvae_layernorm_bwd(int B, int N, const float* dy, int64_t lddy, 
     MMVAE_LAUNCH(layernorm_bwd_kernel, dim3(ceil_div_i(B, 4)), dim3(256), 0, (hipStream_t)stream, B, N, dy,
                        lddy, y, ldy, save_invstd, dx, lddx);
     MMVAE_LAUNCH_CHECK();
+    return MMVAE_OK;
+}
+
+extern "C" int mmvae_fc_rowtail_fwd(int B, int N, const float* in, int64_t ld_in, int n_slabs, const float* bias, float eps,
+                                    int training, int relu, const uint8_t* keep_mask, float dropout_p, float* y_out,
+                                    float* a_out, float* d_out, int64_t ld_out, float* save_invstd,
+                                    mmvae_stream_t stream) {
+    if (B <= 0 || N <= 0 || !in || !d_out || n_slabs < 1 || ld_in < N || ld_out < N || !(eps >= 0.f)) return MMVAE_ERR_ARG;
+    if (keep_mask && (!training || dropout_p < 0.f || dropout_p >= 1.f)) return MMVAE_ERR_ARG;
+    if (training && !save_invstd) return MMVAE_ERR_ARG;
+    RowFwdArgs a = {};
+    a.in = in;
+    a.ld_in = ld_in;
+    a.slab_stride = (int64_t)B * ld_in;
+    a.n_slabs = n_slabs;
+    a.bias = bias;
+    a.eps = eps;
+    a.relu = relu;
+    a.mask = keep_mask;
+    a.keep_scale = keep_mask ? 1.0f / (1.0f - dropout_p) : 1.f;
+    a.y_out = training ? y_out : nullptr;  // eval mode: nothing is saved for a backward pass
+    a.a_out = training ? a_out : nullptr;
+    a.d_out = d_out;
+    a.ld_out = ld_out;
+    a.save_invstd = training ? save_invstd : nullptr;
+    a.B = B;
+    a.N = N;
+    const dim3 grid(ceil_div_i(B, 4)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (N <= 256)
+        MMVAE_LAUNCH(fc_rowtail_fwd_kernel<4>, grid, block, 0, s, a);
+    else if (N <= 512)
+        MMVAE_LAUNCH(fc_rowtail_fwd_kernel<8>, grid, block, 0, s, a);
+    else if (N <= 768)
+        MMVAE_LAUNCH(fc_rowtail_fwd_kernel<12>, grid, block, 0, s, a);
+    else if (N <= 1024)
+        MMVAE_LAUNCH(fc_rowtail_fwd_kernel<16>, grid, block, 0, s, a);
+    else
+        MMVAE_LAUNCH(fc_rowtail_fwd_loop_kernel, grid, block, 0, s, a);
+    MMVAE_LAUNCH_CHECK();
+    return MMVAE_OK;
+}
+
+extern "C" int mmvae_fc_rowtail_bwd(int B, int N, const float* din, int64_t ld_in, int n_slabs, const float* addend,
+                                    const float* row_scale, const uint8_t* keep_mask, float dropout_p, int relu,
+                                    const float* act, const float* y, const float* save_invstd, float* dz_out,
+                                    int64_t ld_out, float* dbias, float* workspace, size_t workspace_bytes,
+                                    mmvae_stream_t stream) {
+    if (B <= 0 || N <= 0 || !din || !y || !save_invstd || !dz_out || n_slabs < 1 || ld_in < N || ld_out < N)
+        return MMVAE_ERR_ARG;
+    if (relu && !act) return MMVAE_ERR_ARG;
+    if (keep_mask && (dropout_p < 0.f || dropout_p >= 1.f)) return MMVAE_ERR_ARG;
+    const int RC = ceil_div_i(B, RPC);
+    if (dbias && !workspace) return MMVAE_ERR_WORKSPACE;
+    if (workspace && workspace_bytes < (size_t)RC * (size_t)N * sizeof(float)) return MMVAE_ERR_WORKSPACE;
+    RowBwdArgs a = {};
+    a.din = din;
+    a.ld_in = ld_in;
+    a.slab_stride = (int64_t)B * ld_in;
+    a.n_slabs = n_slabs;
+    a.addend = addend;
+    a.row_scale = row_scale;
+    a.mask = keep_mask;
+    a.keep_scale = keep_mask ? 1.0f / (1.0f - dropout_p) : 1.f;
+    a.relu = relu;
+    a.act = act;
+    a.y = y;
+    a.save_invstd = save_invstd;
+    a.dz_out = dz_out;
+    a.ld_out = ld_out;
+    a.ws = workspace;
+    a.B = B;
+    a.N = N;
+    const dim3 grid(RC), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (N <= 256)
+        MMVAE_LAUNCH(fc_rowtail_bwd_kernel<4>, grid, block, 0, s, a);
+    else if (N <= 512)
+        MMVAE_LAUNCH(fc_rowtail_bwd_kernel<8>, grid, block, 0, s, a);
+    else if (N <= 768)
+        MMVAE_LAUNCH(fc_rowtail_bwd_kernel<12>, grid, block, 0, s, a);
+    else if (N <= 1024)
+        MMVAE_LAUNCH(fc_rowtail_bwd_kernel<16>, grid, block, 0, s, a);
+    else {
+        MMVAE_LAUNCH(fc_rowtail_bwd_loop_kernel, dim3(ceil_div_i(B, 4)), block, 0, s, a);
+        if (workspace) {  // the chunk partials of dz by the column kernel (same [RC][N] layout)
+            MMVAE_LAUNCH_CHECK();
+            BwdArgs c = {};
+            c.din = dz_out;
+            c.ld_in = ld_out;
+            c.slab_stride = (int64_t)B * ld_out;
+            c.n_slabs = 1;
+            c.keep_scale = 1.f;
+            c.ld_out = ld_out;
+            c.ws = workspace;
+            c.B = B;
+            c.N = N;
+            c.RC = RC;
+            MMVAE_LAUNCH(fc_bwd_stats_kernel<false>, dim3(ceil_div_i(N, CW), RC), dim3(CT), 0, s, c);
+        }
+    }
+    MMVAE_LAUNCH_CHECK();
+    if (dbias) {
+        MMVAE_LAUNCH(fc_colsum_finish_kernel, dim3(ceil_div_i(N, 256)), dim3(256), 0, s, workspace, RC, N, dbias);
+        MMVAE_LAUNCH_CHECK();
+    }
     return MMVAE_OK;
 }

@@ -16,9 +16,11 @@ Per-step host values (KL weight) live in device scalars the kernels read, so the
 Under data parallelism the program is cut at the gradient all-reduce points (RCCL over the flat arenas) into several
 graphs.  Conditional layers (CLVAE) run inside the program through the grouped kernels: the per-cell
 condition indices, the per-condition row groups and the optimiser's job table of the blocks that took part are
-per-step HOST values, uploaded into static device tables before the replay (CondProgram).  Configurations outside this
-shape (LayerNorm / non-ReLU activations in the FC blocks, conditional blocks that are not one Linear, conditional
-layers under data parallelism) use the module path.
+per-step HOST values, uploaded into static device tables before the replay (CondProgram).  LayerNorm layers of the FC
+blocks run through the fused row tail (PlanEmit.fwd_layer).  Configurations outside this shape use the module path,
+and CMMVAEModel says so once (StepEngine.decline_reason names them: non-ReLU activations in the FC blocks, LayerNorm
+in an adversary's encoder, on an expert encoder's first or an expert decoder's last layer, conditional blocks that
+are not one Linear).
 """
 from __future__ import annotations
 
@@ -31,7 +33,7 @@ import torch
 from . import _lib, dist as mdist, rng
 from .constants import REGISTRY_KEYS as RK
 from .engine_adv import PlanAdversaries
-from .engine_common import ACC, NN, NT, SQ_FUSED_SLOTS, TN, _LayerRef, _PlaneBuf, _p, _supported_block
+from .engine_common import ACC, NN, NT, SQ_FUSED_SLOTS, TN, _LayerRef, _PlaneBuf, _block_decline, _p
 from .engine_cond import CondProgram
 from .engine_emit import PlanEmit
 from .engine_run import PlanRun
@@ -190,31 +192,57 @@ def plan_layout(st: EngineSettings, *, fork_ok: bool, side_stream: bool, side_st
 
 class StepEngine:
     @staticmethod
-    def try_build(model) -> Optional["StepEngine"]:
+    def decline_reason(model) -> Optional[str]:
+        """Why the captured step programs do not cover `model` (it then trains on the autograd module path), or None
+        when they do.  Reasons that lie in the model's shape come first, the optimisers last."""
         m = model.module
+        if m.vae.encoder.z_transformation is not _identity:
+            return ('the latent distribution is not "normal" (distribution="ln": a '
+                    f"{type(m.vae.encoder.z_transformation).__name__} over the latent sample)")
+        blocks = [("the shared VAE's encoder", m.vae.encoder.fc), ("the shared VAE's decoder", m.vae.decoder)]
+        for eid, e in m.experts.items():
+            blocks += [(f"the encoder of expert {eid!r}", e.encoder), (f"the decoder of expert {eid!r}", e.decoder)]
+        for where, b in blocks:
+            why = _block_decline(b)
+            if why is not None:
+                return f"{where}: {why}"
+        for eid, e in m.experts.items():
+            if hasattr(e.encoder.fc_layers[0], "ln"):
+                return (f"the encoder of expert {eid!r}: LayerNorm on its first (gene-wide) layer, whose product is "
+                        "pipelined across steps and whose weight gradient reads pre-split planes")
+            if hasattr(e.decoder.fc_layers[-1], "ln"):
+                return (f"the decoder of expert {eid!r}: LayerNorm on its last (gene-wide) layer, which is fused with the "
+                        "reconstruction epilogue")
+        for i, adv in enumerate(m.adversarials, start=1):
+            why = _block_decline(adv.encoder, layer_norm=False)
+            if why is not None:
+                return f"the encoder of adversary {i}: {why} (the adversaries' programs have no row tail)"
+            for c, h in adv.heads.items():
+                if len(h.fc_layers) != 1 or len(list(h.fc_layers[0].children())) != 1:
+                    return f"head {c!r} of adversary {i} is not a single Linear"
         cl = getattr(m.vae, "conditionals", None)
         if cl is not None and not EngineSettings.from_env().conditionals:
-            return None
-        if m.vae.encoder.z_transformation is not _identity:
-            return None
-        blocks = [m.vae.encoder.fc, m.vae.decoder]
-        for e in m.experts.values():
-            blocks += [e.encoder, e.decoder]
-        for adv in m.adversarials:
-            blocks.append(adv.encoder)
-            for h in adv.heads.values():
-                if len(h.fc_layers) != 1 or len(list(h.fc_layers[0].children())) != 1:
-                    return None
-        if not all(_supported_block(b) for b in blocks):
-            return None
+            return "conditional layers with MMVAE_ENGINE_CONDITIONALS=0"
         opts = model.optimizers()
         if not all(isinstance(o, HipAdam) and o._hip for o in opts):
-            return None
+            return "an optimiser that is not the HIP Adam (mmvae_amd.optim.HipAdam on device arenas)"
         if cl is not None:
             # (ranks see different conditions: the blocks that step are the UNION over the ranks, CondProgram.load)
             if not CondProgram.supported(cl, model.get_optimizers()["vae"], m.vae.encoder.mean_encoder.out_features):
-                return None
-        return StepEngine(model)
+                return ("conditional blocks that are not one Linear (+ LayerNorm) of the latent width each, all in the "
+                        "shared VAE's optimiser")
+        return None
+
+    @staticmethod
+    def try_build(model, on_decline=None) -> Optional["StepEngine"]:
+        """The engine for `model`, or None when decline_reason() names a cause; `on_decline(reason)` is then called
+        (CMMVAEModel warns with it)."""
+        why = StepEngine.decline_reason(model)
+        if why is None:
+            return StepEngine(model)
+        if on_decline is not None:
+            on_decline(why)
+        return None
 
     def __init__(self, model, settings: Optional[EngineSettings] = None):
         self.model = model
@@ -1048,7 +1076,7 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
             self._emit(lib.mmvae_split_planes_f32, *job)
         self._x_split_jobs = []
         last = self.dec_layers[-1]
-        if not (last.relu and last.bn is None and last.p == 0):
+        if not (last.relu and last.bn is None and last.ln is None and last.p == 0):
             raise _lib.HipLibraryError("engine: the last decoder layer must be Linear+ReLU (fused recon epilogue)")
         last.inp, last.ld_inp, last.rows = cur, ld, R
         T = lib.mmvae_recon_tiles(G)

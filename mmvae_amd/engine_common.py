@@ -2,6 +2,8 @@
 staging ring, layer records and bf16-plane buffers."""
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 import torch.nn as nn
 
@@ -78,20 +80,27 @@ class _LayerRef:
         self.bn = bn
         if bn is not None:
             self.ggamma, self.gbeta = grad_of(bn.weight), grad_of(bn.bias)
+        ln = getattr(seq, "ln", None)
+        self.ln = float(ln.eps) if ln is not None else None  # LayerNorm(no affine) behind the Linear / BatchNorm: its eps
         self.relu = isinstance(getattr(seq, "af", None), nn.ReLU)
         dr = getattr(seq, "dr", None)
         self.p = float(dr.p) if dr is not None else 0.0
         self.return_hidden = return_hidden and hasattr(seq, "af")
 
 
-def _supported_block(block: FCBlock) -> bool:
-    for seq in block.fc_layers:
-        if hasattr(seq, "ln"):
-            return False
+def _block_decline(block: FCBlock, layer_norm: bool = True) -> Optional[str]:
+    """Why the engine's layer programs do not take this FCBlock, or None when they do.  `layer_norm=False`: a block
+    whose program has no row tail (the adversaries' fused passes)."""
+    for i, seq in enumerate(block.fc_layers):
+        ln = getattr(seq, "ln", None)
+        if ln is not None and not layer_norm:
+            return f"LayerNorm in layer {i}"
+        if ln is not None and (ln.weight is not None or ln.bias is not None):
+            return f"LayerNorm with an elementwise affine in layer {i}"
         af = getattr(seq, "af", None)
         if af is not None and not isinstance(af, nn.ReLU):
-            return False
-    return True
+            return f"activation {type(af).__name__} in layer {i} (the layer kernels fuse ReLU only)"
+    return None
 
 
 class _PlaneBuf:

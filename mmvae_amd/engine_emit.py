@@ -300,6 +300,8 @@ class PlanEmit:
         if not self._x_split_jobs:
             return None
         p_drop = l.p if self.mode == "train" else 0.0
+        if l.ln is not None and l.bn is None:
+            return None  # this layer's tail is the row kernel
         if l.bn is None and p_drop == 0 and self._plan_gemm(NT, rows, l.n_out, l.n_in) == 1:
             return None  # this layer's tail is fused into its GEMM
         return self._x_split_jobs.pop(0)
@@ -393,6 +395,9 @@ class PlanEmit:
         p_drop = l.p if training else 0.0
         self._fcws_bytes = max(self._fcws_bytes, self.lib.mmvae_fc_workspace_bytes(rows, l.n_out))
         sk = self._plan_gemm(NT, rows, l.n_out, l.n_in)
+        l.y = l.ln_invstd = l.bn_out = l.dy = None
+        if l.ln is not None:
+            return self._fwd_layer_ln(tag, l, cur, ld_cur, rows, training, p_drop, sk, planes_out, split_job, slabs_from)
         if l.bn is None and p_drop == 0 and sk == 1:
             self.gemm(NT, rows, l.n_out, l.n_in, cur, ld_cur, l.W, l.n_in, l.d, l.n_out, bias=l.b,
                       flags=RELU if l.relu else 0)
@@ -404,6 +409,13 @@ class PlanEmit:
             S = sk
         else:
             S = self.gemm_raw(NT, rows, l.n_out, l.n_in, cur, ld_cur, l.W, l.n_in)
+        self._emit_col_fwd(l, rows, S, slabs_from, training, l.relu, l.mask, p_drop, l.a, l.d, planes_out, split_job)
+        return l.d
+
+    def _emit_col_fwd(self, l: _LayerRef, rows: int, S: int, slabs_from, training: bool, relu: bool, mask, p_drop: float,
+                      a_out, d_out, planes_out=None, split_job=None):
+        """The column kernel of a layer tail over S split-K slabs (the shared slab buffer, or `slabs_from`): bias,
+        BatchNorm, and -- as the caller asks -- ReLU and the keep mask, into a_out / d_out."""
         bnp = None
         if l.bn is not None:
             bn = l.bn
@@ -414,8 +426,8 @@ class PlanEmit:
 
         def call():
             args = (rows, l.n_out, slabs_from.data_ptr() if slabs_from is not None else plan.slab.data_ptr(), l.n_out, S, _p(l.b),
-                    C.byref(bnp) if bnp is not None else None, int(training), int(l.relu),
-                    _p(l.mask), p_drop, _p(l.z), _p(l.a), _p(l.d), l.n_out, _p(l.mean), _p(l.invstd),
+                    C.byref(bnp) if bnp is not None else None, int(training), int(relu),
+                    _p(mask), p_drop, _p(l.z), _p(a_out), _p(d_out), l.n_out, _p(l.mean), _p(l.invstd),
                     plan.fcws.data_ptr(), plan.fcws.numel() * 4)
             if split_job is not None:  # extra workgroups of the tail split an unrelated matrix (the input batch)
                 rc = plan.lib.mmvae_fc_epilogue_fwd_split(*args, *split_job, _s())
@@ -427,6 +439,39 @@ class PlanEmit:
                 raise _lib.HipLibraryError(f"mmvae_fc_epilogue_fwd failed with code {rc}")
 
         self._cur.append(call)
+
+    def _fwd_layer_ln(self, tag: str, l: _LayerRef, cur, ld_cur: int, rows: int, training: bool, p_drop: float, sk: int,
+                      planes_out, split_job, slabs_from):
+        """A layer with LayerNorm: Linear -> [BatchNorm] -> LayerNorm -> [ReLU] -> [Dropout].  The GEMM always leaves raw
+        slabs (bias and ReLU do not commute with the row statistics); without BatchNorm ONE row-kernel launch sums them,
+        adds the bias, normalises, activates and drops (mmvae_fc_rowtail_fwd).  With BatchNorm the column kernel runs
+        first (bias + BatchNorm only, into `.bn`) and the row tail follows over its output.  Saved for the backward
+        pass: `.y` (the normalised rows, where ReLU or dropout make them differ from `.d`) and `.invstd.rows`."""
+        eng = self.eng
+        if slabs_from is not None:
+            assert tuple(slabs_from.shape) == (sk, rows, l.n_out) and slabs_from.is_contiguous()
+            S = sk
+        else:
+            S = self.gemm_raw(NT, rows, l.n_out, l.n_in, cur, ld_cur, l.W, l.n_in)
+        l.y = eng.buf(f"{tag}.y", (rows, l.n_out)) if (training and (l.relu or p_drop > 0)) else None
+        l.ln_invstd = eng.buf(f"{tag}.invstd.rows", (rows,)) if training else None
+        if l.bn is not None:
+            l.bn_out = eng.buf(f"{tag}.bn", (rows, l.n_out))
+            l.dy = eng.buf(f"{tag}.dy", (rows, l.n_out)) if training else None  # gradient between the two norms
+            self._emit_col_fwd(l, rows, S, slabs_from, training, False, None, 0.0, None, l.bn_out, None, split_job)
+            S = 1
+        plan, src, bias = self, l.bn_out, (l.b if l.bn is None else None)
+
+        def call():
+            in_ptr = _p(src) if src is not None else (slabs_from.data_ptr() if slabs_from is not None else plan.slab.data_ptr())
+            rc = plan.lib.mmvae_fc_rowtail_fwd(rows, l.n_out, in_ptr, l.n_out, S, _p(bias), l.ln, int(training), int(l.relu),
+                                               _p(l.mask), p_drop, _p(l.y), _p(l.a), _p(l.d), l.n_out, _p(l.ln_invstd), _s())
+            if rc != 0:
+                raise _lib.HipLibraryError(f"mmvae_fc_rowtail_fwd failed with code {rc}")
+
+        self._cur.append(call)
+        if planes_out is not None:  # (the row kernel writes no planes: a split pass of its own)
+            self._emit(self.lib.mmvae_split_planes_f32, rows, l.n_out, _p(l.d), l.n_out, *planes_out.args())
         return l.d
 
     # ---- one layer backward.  din: tensor [rows, n_out] or None (= shared slab buffer holding S_in raw slabs)
@@ -445,13 +490,17 @@ class PlanEmit:
         own_ws = None
         if not has_bn and l.gb is not None:
             own_ws = self._bias_partials(rows, l.n_out, l.gb)
+        after_ln = l.ln is not None
+        if after_ln:  # the row tail first; behind it the column kernel has the BatchNorm's backward left to do, or nothing
+            din, S_in, addend, row_scale = self._bwd_layer_ln(l, din, S_in, addend, row_scale, own_ws)
 
         def call():
             din_ptr = _p(din) if din is not None else plan.slab.data_ptr()
             ws = own_ws if own_ws is not None else plan.fcws
             # `addend` is a gradient on the hidden representation = the activation BEFORE dropout: it bypasses the mask
-            args = (rows, l.n_out, din_ptr, l.n_out, S_in, None, _p(addend), _p(row_scale), _p(l.mask), l.p, int(l.relu),
-                    _p(relu_src) if l.relu else None, _p(l.z), _p(l.bn.weight) if has_bn else None, _p(l.mean),
+            mask, relu = (None, False) if after_ln else (l.mask, l.relu)
+            args = (rows, l.n_out, din_ptr, l.n_out, S_in, None, _p(addend), _p(row_scale), _p(mask), l.p, int(relu),
+                    _p(relu_src) if relu else None, _p(l.z), _p(l.bn.weight) if has_bn else None, _p(l.mean),
                     _p(l.invstd), int(has_bn), _p(l.dz), l.n_out, _p(l.gb) if own_ws is None else None,
                     _p(l.ggamma) if has_bn else None, _p(l.gbeta) if has_bn else None, ws.data_ptr(), ws.numel() * 4)
             if dw_planes is not None:
@@ -461,7 +510,8 @@ class PlanEmit:
             if rc != 0:
                 raise _lib.HipLibraryError(f"mmvae_fc_epilogue_bwd failed with code {rc}")
 
-        self._cur.append(call)
+        if has_bn or not after_ln:  # (a LayerNorm layer without BatchNorm: the row tail has written .dz)
+            self._cur.append(call)
         # dW[n_out, n_in] = dz^T[n_out, rows] . inp[rows, n_in]  -> straight into the gradient arena
         # (an adversary reading the first of K > 1 samples: the rows behind its B input rows are the next sample, not slack)
         k_rows = rows if (self.K > 1 and l.inp is self.z and rows != self.R) else self.kpad(rows)
@@ -484,6 +534,28 @@ class PlanEmit:
                 self.gemm(NN, rows, l.n_in, l.n_out, l.dz, l.n_out, l.W, l.n_in, dx_out, l.n_in, flags=dx_flags,
                           alpha=dx_alpha)
         return 0
+
+    def _bwd_layer_ln(self, l: _LayerRef, din, S_in: int, addend, row_scale, own_ws):
+        """Backward of a LayerNorm layer's row tail (mmvae_fc_rowtail_bwd): keep mask, the gradient on the hidden
+        representation, row weights, ReLU slope and LayerNorm in one launch.  Without BatchNorm it writes `.dz` and the
+        bias gradient's chunk partials (`own_ws`) and nothing is left for the column kernel: returns (None, 0, None,
+        None).  With BatchNorm it writes `.dy`, which the column kernel then takes as its plain incoming gradient:
+        returns (.dy, 1, None, None)."""
+        plan, rows, has_bn = self, l.rows, l.bn is not None
+        out = l.dy if has_bn else l.dz
+        act = (l.a if l.a is not None else l.d) if l.relu else None
+        y = l.y if l.y is not None else l.d
+
+        def call():
+            din_ptr = _p(din) if din is not None else plan.slab.data_ptr()
+            rc = plan.lib.mmvae_fc_rowtail_bwd(
+                rows, l.n_out, din_ptr, l.n_out, S_in, _p(addend), _p(row_scale), _p(l.mask), l.p, int(l.relu), _p(act), _p(y),
+                _p(l.ln_invstd), _p(out), l.n_out, None, _p(own_ws), own_ws.numel() * 4 if own_ws is not None else 0, _s())
+            if rc != 0:
+                raise _lib.HipLibraryError(f"mmvae_fc_rowtail_bwd failed with code {rc}")
+
+        self._cur.append(call)
+        return (l.dy, 1, None, None) if has_bn else (None, 0, None, None)
 
     def _bias_partials(self, rows, N, dbias):
         """A [ceil(rows/32), N] partial-column-sum buffer of its own for one layer + the deferred sum into dbias."""

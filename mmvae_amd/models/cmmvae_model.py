@@ -282,7 +282,13 @@ class CMMVAEModel(BaseModel):
         if self._engine is None:
             from ..engine import StepEngine
 
-            self._engine = StepEngine.try_build(self) or False
+            def said_once(why):  # (once per model: the module path is correct but several times slower)
+                import warnings
+
+                warnings.warn(f"mmvae_amd: the captured step engine does not cover this model ({why}); it runs on the "
+                              "autograd module path (use_engine=False silences this)")
+
+            self._engine = StepEngine.try_build(self, on_decline=said_once) or False
         return self._engine or None
 
 

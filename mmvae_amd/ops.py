@@ -456,6 +456,62 @@ def layernorm_bwd(dy: torch.Tensor, y: torch.Tensor, invstd: torch.Tensor):
     return dx
 
 
+def fc_rowtail_fwd(inp: torch.Tensor, bias: Optional[torch.Tensor] = None, *, eps: float = 1e-5, training: bool = True,
+                   relu: bool = False, keep_mask: Optional[torch.Tensor] = None, dropout_p: float = 0.0):
+    """Fused tail of a LayerNorm layer (mmvae_fc_rowtail_fwd).  inp: [B,N] or split-K slabs [S,B,N].  Returns
+    dict(y, a, d, invstd): the normalised rows, the activation before dropout, the layer output, 1 / std per row
+    (y, a alias d where they hold the same values; eval mode returns d only)."""
+    lib = _lib.load()
+    _chk(inp, "inp"), _chk(bias, "bias"), _chk(keep_mask, "keep_mask", torch.uint8)
+    if inp.dim() == 2:
+        inp = inp.unsqueeze(0)
+    if not inp.is_contiguous():
+        raise ValueError("inp must be contiguous")
+    S, B, N = inp.shape
+    dev = inp.device
+    if keep_mask is not None and (tuple(keep_mask.shape) != (B, N) or not keep_mask.is_contiguous()):
+        raise ValueError("keep_mask must be contiguous [B,N] uint8")
+    new = lambda: torch.empty((B, N), dtype=torch.float32, device=dev)  # noqa: E731
+    d = new()
+    a = new() if (training and keep_mask is not None) else None
+    y = new() if (training and (relu or keep_mask is not None)) else None
+    invstd = torch.empty(B, dtype=torch.float32, device=dev) if training else None
+    rc = lib.mmvae_fc_rowtail_fwd(B, N, _ptr(inp), N, S, _ptr(bias), float(eps), int(training), int(relu), _ptr(keep_mask),
+                                  float(dropout_p), _ptr(y), _ptr(a), _ptr(d), N, _ptr(invstd), _stream())
+    _lib.check(rc, "mmvae_fc_rowtail_fwd")
+    a = a if a is not None else d
+    return {"y": y if y is not None else a, "a": a, "d": d, "invstd": invstd}
+
+
+def fc_rowtail_bwd(din: torch.Tensor, y: torch.Tensor, invstd: torch.Tensor, *, addend: Optional[torch.Tensor] = None,
+                   row_scale: Optional[torch.Tensor] = None, keep_mask: Optional[torch.Tensor] = None,
+                   dropout_p: float = 0.0, relu: bool = False, act: Optional[torch.Tensor] = None, want_dbias: bool = True):
+    """Backward of fc_rowtail_fwd (mmvae_fc_rowtail_bwd).  din: [B,N] or slabs [S,B,N]; `addend`: gradient on the
+    activation before dropout (bypasses the keep mask).  Returns (dz, dbias or None)."""
+    lib = _lib.load()
+    _chk(din, "din")
+    if din.dim() == 2:
+        din = din.unsqueeze(0)
+    if not din.is_contiguous():
+        raise ValueError("din must be contiguous")
+    S, B, N = din.shape
+    dev = din.device
+    for name, t in (("addend", addend), ("act", act), ("y", y)):
+        _chk(t, name)
+        if t is not None and (tuple(t.shape) != (B, N) or not t.is_contiguous()):
+            raise ValueError(f"{name} must be contiguous [B,N]")
+    _chk(row_scale, "row_scale"), _chk(invstd, "invstd"), _chk(keep_mask, "keep_mask", torch.uint8)
+    dz = torch.empty((B, N), dtype=torch.float32, device=dev)
+    dbias = torch.empty(N, dtype=torch.float32, device=dev) if want_dbias else None
+    nws = (B + 31) // 32 * N * 4 if want_dbias else 0
+    ws = workspace(nws, dev, "fc") if want_dbias else None
+    rc = lib.mmvae_fc_rowtail_bwd(B, N, _ptr(din), N, S, _ptr(addend), _ptr(row_scale), _ptr(keep_mask), float(dropout_p),
+                                  int(relu), _ptr(act), _ptr(y), _ptr(invstd), _ptr(dz), N, _ptr(dbias), _ptr(ws), nws,
+                                  _stream())
+    _lib.check(rc, "mmvae_fc_rowtail_bwd")
+    return dz, dbias
+
+
 def reparam_kl_fwd(mu: torch.Tensor, a_raw: torch.Tensor, eps: Optional[torch.Tensor], var_eps: float = 1e-4,
                    want_stats: bool = True):
     """mu, a_raw [B,Z]; eps [K,B,Z] or [B,Z] or None.  Returns (std [B,Z], z [K,B,Z]|None, kl_row [B], stat_row [2,B]|None)."""

@@ -109,6 +109,33 @@ def build_model(experts: Dict[str, int], *, latent_dim: int = 128, h1: int = 102
                        autograd_config=AutogradConfig(clip(), clip(), clip()), use_engine=use_engine)
 
 
+def build_layernorm_core_model(experts: Dict[str, int], *, latent_dim: int = 128, h1: int = 1024, dropout: float = 0.1,
+                               n_samples: int = 1, use_engine: bool = True, seed: int = 0):
+    """The core of the reference's newest model file (configs/model/configV3.yaml:16-45) without its conditional layers:
+    the shared VAE's encoder is Linear -> LayerNorm(no affine) -> ReLU on all three layers [768, 512, 256, 256] with
+    return_hidden [false, true, true], its decoder [Z, 256, 256, 512, 768]; experts [G, h1, 768] (BatchNorm, dropout)
+    and [768, h1, G]."""
+    from .config import AutogradConfig, GradientClipConfig
+    from .models import CMMVAEModel
+    from .modules import CMMVAE, CLVAE, base
+
+    def cfg(layers, **kw):
+        return base.FCBlockConfig(layers=list(layers), activation_fn=nn.ReLU, **kw)
+
+    torch.manual_seed(seed)
+    exps = [base.Expert(eid, cfg([G, h1, 768], dropout_rate=dropout, use_batch_norm=True), cfg([768, h1, G]))
+            for eid, G in experts.items()]
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        vae = CLVAE(latent_dim=latent_dim,
+                    encoder_config=cfg([768, 512, 256, 256], use_layer_norm=True, return_hidden=[False, True, True]),
+                    decoder_config=cfg([latent_dim, 256, 256, 512, 768]))
+    vae.encoder.n_samples = n_samples
+    clip = lambda: GradientClipConfig(val=10, algorithm="norm")  # noqa: E731
+    return CMMVAEModel(CMMVAE(vae, base.Experts(exps), None), autograd_config=AutogradConfig(clip(), clip(), clip()),
+                       use_engine=use_engine)
+
+
 def flops_per_cell(G: int, K: int = 1, h1: int = 1024, h2: int = 512, hv: int = 256, Z: int = 128,
                    mode: str = "train") -> float:
     """Algorithmic FLOPs per cell of one step (SURVEY 8d).  train: fwd + dW everywhere + dX except the input layer;
