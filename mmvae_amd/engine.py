@@ -190,6 +190,21 @@ def plan_layout(st: EngineSettings, *, fork_ok: bool, side_stream: bool, side_st
         prefetch_cap=st.prefetch_adv if adv_forks else st.prefetch, prefetch_side2=adv_forks)
 
 
+# Plan keys.  Training programs: (mode, expert, B, K, explicit, slabs ahead, target, pointer, stride); forward-only ones the
+# same without "slabs ahead" and "target".  pointer / stride: the current batch read in place, (0, 0) = through the
+# expert's static input buffer.  target: None, or (expert, pointer, shape, stride) of the announced batch the program
+# computes ahead for; pointer 0 = through that expert's static input buffer.
+def _key_pointer(key: tuple) -> int:
+    """The caller's pointer a plan reads its batch from, 0 when it reads the static input buffer."""
+    return key[-2]
+
+
+def _key_target(key: tuple):
+    """The announced batch a training plan reads IN PLACE (a caller's pointer), else None."""
+    t = key[6] if str(key[0]).startswith("train") else None
+    return t if (t is not None and t[1] != 0) else None
+
+
 class StepEngine:
     @staticmethod
     def decline_reason(model) -> Optional[str]:
@@ -316,11 +331,14 @@ class StepEngine:
         for opt in opts_list:  # torch-side readers of the moments / parameters wait for updates left on another stream
             opt.settle = lambda me=me: me() is not None and me().flush()
         # software pipelining across steps: what the last training program computed ahead for the next one
-        # (training_step, "prefetch"): None or a dict(eid, ptr, shape, stride, version, w_version, slabs)
+        # (training_step, "prefetch"): None or a dict(eid, x, sig, w_version, slabs).  Both records hold the ANNOUNCED TENSOR
+        # itself: the next step is recognised by identity (`is`) on top of its signature, and while the record lives the
+        # allocator cannot hand the tensor's address to another batch.  Each lives for one step: the next training step
+        # takes both; a forward-only step, a withdrawn hint, dropped plans and close() drop them (_drop_lookahead).
         self._prefetched: Optional[dict] = None
         self.prefetch_stats = {"issued": 0, "consumed": 0, "discarded": 0, "staged_ahead": 0}
         self._next_seen: Dict[tuple, int] = {}   # announced batches by (expert, pointer, stride, shape): resident or streamed?
-        self._staged: Dict[str, tuple] = {}      # expert -> (pointer, shape, stride, version) of the batch in its static input buffer
+        self._staged: Optional[tuple] = None     # (expert, tensor, signature) of the batch staged ahead into x_static.<expert>
 
     def _configure_parallel(self) -> None:
         """Overlapped data parallelism (default whenever gradients are exchanged).  The active expert's parameters are
@@ -399,7 +417,19 @@ class StepEngine:
                 p.release()
         self._plans = {k: p for k, p in self._plans.items() if not str(k[0]).startswith("train")}
         self._ptr_seen.clear()
-        self._prefetched = None
+        self._drop_lookahead()
+
+    def _drop_lookahead(self) -> None:
+        """Forget what the last training step prepared for the announced batch (its first product, its staged copy): the
+        step that comes next computes and stages for itself.  Releases the references to the announced tensor."""
+        if self._prefetched is not None:
+            self.prefetch_stats["discarded"] += 1
+        self._prefetched = self._staged = None
+
+    def withdraw_hint(self) -> None:
+        """The batch announced to the last training step will not be trained next (CMMVAEModel.withdraw_hint: a loop that
+        stops early, mmvae_amd.trainer.Lookahead's consumer breaking out)."""
+        self._drop_lookahead()
 
     DP_TUNE_WARM, DP_TUNE_STEPS = 12, 12
 
@@ -508,6 +538,7 @@ class StepEngine:
             p.release()
         self._plans = {}
         self._ptr_seen.clear()
+        self._drop_lookahead()
         # sharded expert updates leave (world - 1) / world of the Adam moments on other ranks: gather them while the
         # process group is alive, so that a later state_dict() -- on one rank only, or after destroy_process_group() -- is
         # local (COLLECTIVE under data parallelism: every rank closes its engine, like every rank takes every step)
@@ -546,41 +577,87 @@ class StepEngine:
         60 530 / 52 437 genes)."""
         return l0_in % 4 != 0 or B % 32 != 0
 
-    def _select_input(self, x: torch.Tensor, base_key: tuple, needs_slack: bool = True):
+    def _select_input(self, x: torch.Tensor, base_key: tuple, needs_slack: bool = True, target=None, staged=None):
         """Plan selection: graphs are keyed by the input pointer once a pointer has been seen twice (resident
-        batches); otherwise the batch is copied into a static buffer.  Returns (plan key, the tensor the plan reads).
+        batches); otherwise the batch is copied into a static buffer.  Returns (plan key, the tensor the plan reads, the
+        tensor it reads the announced batch from or None).
         needs_slack: some kernel of the program reads the batch as a rows-contiguous fp32 GEMM operand (the first layer's
         weight gradient without planes): 16-byte groups that reach past a row's end when the gene count is not a multiple
-        of 4, and zero rows behind a batch that is not a multiple of 32 (kpad)."""
+        of 4, and zero rows behind a batch that is not a multiple of 32 (kpad).
+        target: (expert, tensor) of the batch announced for the next step (training programs; _prefetch_target): the key
+        then carries where the program reads it from -- in place when it is resident and the budget allows, else the next
+        expert's static input buffer, filled NOW (_stage_next).
+        staged: the record the previous step left when it staged THIS batch ahead (taken by the caller)."""
         B = x.shape[0]
-        if x.layout == torch.sparse_csr:  # CSR batch: densified by one HIP pass straight into the static input buffer
+        free = (0, 0)
+        t_static = t_ptr = None
+        if target is not None:
+            eid_n, x_n = target
+            t_static = (eid_n, 0, tuple(x_n.shape), 0)  # (through x_static.<eid_n>: one buffer per expert and shape)
+            if self._announced_resident(eid_n, x_n):
+                t_ptr = (eid_n, x_n.data_ptr(), tuple(x_n.shape), x_n.stride(0))
+        train = str(base_key[0]).startswith("train")
+        want_t = t_ptr or t_static
+        want_base = base_key + ((want_t,) if train else ())
+        cur = None
+        if x.layout != torch.sparse_csr:  # (a CSR batch is densified by one HIP pass straight into the static input buffer)
+            pkey = want_base + (x.data_ptr(), x.stride(0))
+            seen = self._ptr_seen.get(pkey, 0)
+            if len(self._ptr_seen) > 4096:
+                self._ptr_seen.clear()
+            self._ptr_seen[pkey] = seen + 1
+            # a caller's tensor has no slack behind it: with a gene count that is not a multiple of 4, or a batch that is
+            # not a multiple of 32 (kpad reads zero rows behind the batch), it is always staged
+            direct_ok = (x.shape[1] % 4 == 0 and B % 32 == 0) or not needs_slack
+            if direct_ok and (pkey in self._plans or seen >= 1):
+                cur = (x.data_ptr(), x.stride(0))
+        tsig, cur = self._pick_program(base_key, train, t_ptr, t_static, cur)
+        x_t = None
+        if target is not None:
+            x_t = x_n if tsig is t_ptr else self._stage_next(eid_n, x_n)
+        key = base_key + ((tsig,) if train else ()) + (cur or free)
+        if cur is not None:
+            return key, x, x_t
+        x_in = self.buf(f"x_static.{base_key[1]}", (B, x.shape[1]))
+        if staged is not None and staged[0] == base_key[1] and staged[1] is x and staged[2] == self._batch_sig(x):
+            pass  # the previous step staged (densified) this very batch when it was announced (_stage_next)
+        elif x.layout == torch.sparse_csr:
             from . import ops
 
-            x_in = self.buf(f"x_static.{base_key[1]}", (B, x.shape[1]))
-            if self._staged.pop(base_key[1], None) != self._batch_sig(x):  # (else: densified when it was announced)
-                ops.csr_to_dense(x, out=x_in)
-            return base_key + (0, 0), x_in
-        pkey = base_key + (x.data_ptr(), x.stride(0))
-        seen = self._ptr_seen.get(pkey, 0)
-        self._ptr_seen[pkey] = seen + 1
-        n_ptr_plans = sum(1 for k in self._plans if k[-2] != 0)
-        # a caller's tensor has no slack behind it: with a gene count that is not a multiple of 4, or a batch that is
-        # not a multiple of 32 (kpad reads zero rows behind the batch), it is always staged
-        direct_ok = (x.shape[1] % 4 == 0 and B % 32 == 0) or not needs_slack
-        if direct_ok and (pkey in self._plans or (seen >= 1 and n_ptr_plans < MAX_POINTER_PLANS)):
-            return pkey, x
-        x_in = self.buf(f"x_static.{base_key[1]}", (B, x.shape[1]))
-        if self._staged.pop(base_key[1], None) == self._batch_sig(x):
-            pass  # the previous step staged this very batch when it was announced (_stage_next)
+            ops.csr_to_dense(x, out=x_in)
         elif x.is_contiguous():  # own 16-byte copy kernel: the runtime's blit kernel reaches < 1 TB/s here
             from . import ops
 
             ops.axpby(1.0, x, 0.0, x_in)
         else:
             x_in.copy_(x)
-        if len(self._ptr_seen) > 4096:
-            self._ptr_seen.clear()
-        return base_key + (0, 0), x_in
+        return key, x_in, x_t
+
+    def _pick_program(self, base_key: tuple, train: bool, t_ptr, t_static, cur):
+        """(target signature, current batch's (pointer, row stride) or None) of the program to run, out of what the step
+        would like: the current batch in place (`cur`: a resident pointer, else None) and the announced one in place
+        (`t_ptr`: resident, else None; `t_static`: through the static buffer; both None: nothing announced).  A program
+        that exists is always taken.  A NEW program whose key holds a caller's pointer -- the current batch's, the
+        announced batch's, or both -- is built only while fewer than MAX_POINTER_PLANS programs are keyed by a current
+        batch's pointer, and reads the announced batch in place only when that batch is one of at most MAX_POINTER_PLANS
+        distinct in-place targets.  Beyond that: an existing program that stages one of the two, else the pointer-free
+        one that stages both.  Train keys: (mode, expert, B, K, explicit, slabs ahead, target, pointer, stride)."""
+        def key(t, c):
+            return base_key + ((t,) if train else ()) + (c or (0, 0))
+
+        want_t = t_ptr or t_static
+        if (t_ptr is None and cur is None) or key(want_t, cur) in self._plans:
+            return want_t, cur
+        if sum(1 for k in self._plans if _key_pointer(k) != 0) < MAX_POINTER_PLANS:
+            if t_ptr is None:
+                return want_t, cur
+            targets = {_key_target(k) for k in self._plans} - {None}
+            return (t_ptr if (t_ptr in targets or len(targets) < MAX_POINTER_PLANS) else t_static), cur
+        if cur is not None and key(t_static, cur) in self._plans:
+            return t_static, cur
+        if t_ptr is not None and key(t_ptr, None) in self._plans:
+            return t_ptr, None
+        return t_static, None
 
     @staticmethod
     def _dense_f32(x: torch.Tensor) -> torch.Tensor:
@@ -610,7 +687,8 @@ class StepEngine:
         B = x.shape[0]
         # (forward-only programs read the batch through the K-contiguous forward GEMM and the reconstruction epilogue's
         # guarded loads only: any caller's tensor serves as it is)
-        key, x_in = self._select_input(x, (mode, expert_id, B, 1, explicit), needs_slack=False)
+        self._drop_lookahead()  # (the static input buffers are rewritten; a training step behind this one starts afresh)
+        key, x_in, _ = self._select_input(x, (mode, expert_id, B, 1, explicit), needs_slack=False)
         plan = self._plans.get(key)
         if plan is None:
             plan = _Plan(self, expert_id, B, 1, explicit, x_in, mode=mode)
@@ -684,30 +762,32 @@ class StepEngine:
             return ("csr", v.data_ptr(), c.data_ptr(), x.col_indices().data_ptr(), tuple(x.shape), v._version, c._version)
         return (x.data_ptr(), tuple(x.shape), x.stride(0), x._version)
 
+    def _announced_resident(self, eid_n: str, x_n: torch.Tensor) -> bool:
+        """Counts the announcement; has this (dense) batch been announced at least twice before -- a resident one?"""
+        if x_n.layout == torch.sparse_csr:
+            return False
+        k = (eid_n, x_n.data_ptr(), x_n.stride(0), tuple(x_n.shape))
+        seen = self._next_seen.get(k, 0)
+        if len(self._next_seen) > 4096:
+            self._next_seen.clear()
+        self._next_seen[k] = seen + 1
+        return seen >= 2
+
     def _stage_next(self, eid_n: str, x_n: torch.Tensor) -> torch.Tensor:
-        """The tensor this step's program reads the announced batch from.  A resident batch (its pointer has been announced
-        before) is read in place.  A streamed one -- a new tensor every step -- is copied into the next expert's static
-        input buffer NOW: that is the staging copy its own step would make at its start (_select_input), made one step
-        earlier, so the program's pointers stay the same from step to step (no plan per batch) and the next step finds its
-        input in place (`_staged`)."""
+        """The announced batch copied into the next expert's static input buffer NOW (a resident batch within the
+        pointer budget is read in place instead: _select_input).  That is the staging copy its own step would make at
+        its start, made one step earlier, so the program's pointers stay the same from step to step (no plan per batch)
+        and the next step finds its input in place (`_staged`)."""
         from . import ops
 
         buf = self.buf(f"x_static.{eid_n}", tuple(x_n.shape))
         if x_n.layout == torch.sparse_csr:  # a CSR batch is densified into that buffer by its own step anyway: one step early
             ops.csr_to_dense(x_n, out=buf)
+        elif x_n.is_contiguous():
+            ops.axpby(1.0, x_n, 0.0, buf)
         else:
-            k = (eid_n, x_n.data_ptr(), x_n.stride(0), tuple(x_n.shape))
-            seen = self._next_seen.get(k, 0)
-            if len(self._next_seen) > 4096:
-                self._next_seen.clear()
-            self._next_seen[k] = seen + 1
-            if seen >= 2:
-                return x_n
-            if x_n.is_contiguous():
-                ops.axpby(1.0, x_n, 0.0, buf)
-            else:
-                buf.copy_(x_n)
-        self._staged[eid_n] = self._batch_sig(x_n)
+            buf.copy_(x_n)
+        self._staged = (eid_n, x_n, self._batch_sig(x_n))
         self.prefetch_stats["staged_ahead"] += 1
         return buf
 
@@ -717,7 +797,8 @@ class StepEngine:
         if pf is None:
             return None
         w = self.model.module.experts[eid].encoder.fc_layers[0].lin.weight if eid in self.model.module.experts else None
-        ok = pf["eid"] == eid and w is not None and pf["sig"] == self._batch_sig(x) and pf["w_version"] == w._version
+        ok = (pf["eid"] == eid and w is not None and pf["x"] is x and pf["sig"] == self._batch_sig(x)
+              and pf["w_version"] == w._version)
         self.prefetch_stats["consumed" if ok else "discarded"] += 1
         return pf["slabs"] if ok else None
 
@@ -739,15 +820,15 @@ class StepEngine:
         planes = self._enc_planes(l0.lin.in_features, l0.lin.out_features, hasattr(l0, "bn"), B, K, True, iwae)
         ahead = self._take_prefetched(expert_id, x) if x is x_arg else None  # slabs the previous step left for this one
         if x is not x_arg:
-            self._prefetched = None
+            self._drop_lookahead()
+        staged, self._staged = self._staged, None  # the copy the previous step staged ahead, if it was of this batch
         target = self._prefetch_target(expert_id, B, K, iwae, next_batch)
         hinted = target[1] if target else None  # the caller's tensor: what the next step will be recognised by
+        key, x_in, x_t = self._select_input(x, ("train-iwae" if iwae else "train", expert_id, B, K, explicit,
+                                                ahead.data_ptr() if ahead is not None else 0),
+                                            needs_slack=not planes, target=target, staged=staged)
         if target is not None:
-            target = (target[0], self._stage_next(*target))
-        tsig = (target[0], target[1].data_ptr(), tuple(target[1].shape), target[1].stride(0)) if target else None
-        key, x_in = self._select_input(x, ("train-iwae" if iwae else "train", expert_id, B, K, explicit,
-                                           ahead.data_ptr() if ahead is not None else 0, tsig),
-                                       needs_slack=not planes)
+            target = (target[0], x_t)
         plan = self._plans.get(key)
         if plan is None:
             plan = _Plan(self, expert_id, B, K, explicit, x_in, iwae=iwae, slabs_ahead=ahead, prefetch=target)
@@ -771,7 +852,8 @@ class StepEngine:
         if target is not None:  # this program has computed the next step's first product
             x_n = hinted
             w_n = model.module.experts[target[0]].encoder.fc_layers[0].lin.weight
-            self._prefetched = dict(eid=target[0], sig=self._batch_sig(x_n), w_version=w_n._version, slabs=plan.prefetch_slabs)
+            self._prefetched = dict(eid=target[0], x=x_n, sig=self._batch_sig(x_n), w_version=w_n._version,
+                                    slabs=plan.prefetch_slabs)
             self.prefetch_stats["issued"] += 1
         if plan.cond is not None:
             plan.cond.commit()

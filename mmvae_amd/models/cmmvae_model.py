@@ -180,12 +180,28 @@ class CMMVAEModel(BaseModel):
         this step's latency-bound forward chain (software pipelining across steps, mmvae_amd.engine: same kernels on the
         same operands, bit-identical results; a hint that turns out wrong costs one wasted product).  The hinted tensor
         must stay unmodified until its step.  mmvae_amd.trainer.Trainer and mmvae_amd.data.Lookahead look one batch ahead;
-        the reference's loop (no look-ahead) simply never calls this."""
+        the reference's loop (no look-ahead) simply never calls this.
+        The next step recognises the announced batch by the tensor OBJECT (the engine keeps a reference until then) and by
+        torch's version counter: another tensor at the same address, or a torch in-place write, drops the product.  A
+        write through a raw device pointer -- the `ops.*` ctypes kernels with the tensor as their output, a kernel of the
+        caller's own -- bumps no version counter and cannot be seen: not writing the announced batch that way until its
+        step is the caller's responsibility.  None says that nothing is known about the step after the next one; a loop
+        that will NOT train the batch it announced calls withdraw_hint()."""
         if batch is None:
             self._next_hint = None
             return
         x, _, expert_id = batch
         self._next_hint = (x, expert_id)
+
+    def withdraw_hint(self) -> None:
+        """The announced batch will not be the next training step's after all (the loop stops early, skips it, failed):
+        the pending hint is dropped, and so is what the last step already prepared for that batch (its first product,
+        its staged copy) together with the engine's reference to it.  mmvae_amd.trainer.Lookahead calls this when its
+        consumer stops before the batches are exhausted."""
+        self._next_hint = None
+        engine = getattr(self, "_engine", None)
+        if engine:
+            engine.withdraw_hint()
 
     def gather_optimizer_state(self) -> None:
         """Under data parallelism the engine updates each expert arena sharded (this rank's slice of the Adam moments

@@ -47,7 +47,12 @@ class Lookahead:
     """Wraps a batch iterable and tells the model, before each batch is handed out, which batch comes AFTER it
     (`CMMVAEModel.hint_next_batch`): the step engine then computes the next step's first forward product beside the
     current step's forward chain (software pipelining across steps).  Works around any loop that pulls batches one at a
-    time -- this module's Trainer, or a Lightning Trainer given `Lookahead(dataloader, model)` as its train dataloader."""
+    time -- this module's Trainer, or a Lightning Trainer given `Lookahead(dataloader, model)` as its train dataloader.
+    A consumer that stops early (break, limit_train_batches) leaves a batch announced that will never be trained: the
+    iterator withdraws it when it is closed (`CMMVAEModel.withdraw_hint`; a model without it is told None) -- at the
+    `break` under CPython's reference counting, and when the batches themselves raise.  When the CONSUMER's step raises,
+    the traceback keeps the iterator alive and the withdrawal waits for the exception's release: a loop that catches the
+    error and goes on calls `withdraw_hint()` itself (the engine's identity check holds either way)."""
 
     def __init__(self, batches: Iterable, model):
         self.batches, self.model = batches, model
@@ -61,12 +66,19 @@ class Lookahead:
             cur = next(it)
         except StopIteration:
             return
-        for nxt in it:
-            self.model.hint_next_batch(nxt)
+        exhausted = False
+        try:
+            for nxt in it:
+                self.model.hint_next_batch(nxt)
+                yield cur
+                cur = nxt
+            self.model.hint_next_batch(None)
             yield cur
-            cur = nxt
-        self.model.hint_next_batch(None)
-        yield cur
+            exhausted = True
+        finally:
+            if not exhausted:  # (GeneratorExit at a yield: the consumer stopped; or the batches raised)
+                withdraw = getattr(self.model, "withdraw_hint", None)
+                withdraw() if withdraw is not None else self.model.hint_next_batch(None)
 
 
 class Trainer:

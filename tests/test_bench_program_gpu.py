@@ -119,9 +119,57 @@ def test_bench_program_matches_oracle(config):
     model._engine.close()
 
 
-def _run_c2(steps, env, attach=False, keep_engine=False, config="c2", hints=None):
+_STEP_COUNTS = {}
+
+
+@pytest.fixture(autouse=True)
+def _drop_step_counts():
+    """(the host batches of _step_counts are shared by the runs of ONE test, not kept for the rest of the process)"""
+    yield
+    _STEP_COUNTS.clear()
+
+
+def _step_counts(B, G, i):
+    """The cells of training step `i` of the per-step data mode (host tensor, cached: the hinted and the hint-free run of
+    a comparison train on the same sequence): synthetic_counts(B, G, seed=4001 + 31 * i), different at every step."""
+    from mmvae_amd import synthetic
+
+    k = (B, G, i)
+    if k not in _STEP_COUNTS:
+        _STEP_COUNTS[k] = synthetic.synthetic_counts(B, G, seed=4001 + 31 * i)
+    return _STEP_COUNTS[k]
+
+
+def _rolled_counts(B, G, i):
+    """Cells number `i` of the scenarios that need many different batches cheaply: one of two _step_counts batches with its
+    genes rotated by 37 i + 1 places (a row permutation would leave the batch statistics and the summed losses nearly
+    unchanged; a rotation along the genes meets other weights)."""
+    return torch.roll(_step_counts(B, G, i % 2), 37 * i + 1, dims=1)
+
+
+def _hint_right(i, data, eids):
+    e = eids[(i + 1) % len(eids)]
+    return (*data[e], e)
+
+
+def _hint_unreliable(i, data, eids):
+    if i % 4 == 1:
+        return None                                  # no look-ahead for this step
+    if i % 4 == 2:
+        e = eids[i % len(eids)]                      # the same expert again: must not be computed ahead
+        return (*data[e], e)
+    if i % 4 == 3:
+        e = eids[(i + 1) % len(eids)]                # the right expert, another tensor than the one that will arrive
+        return (data[e][0].clone(), data[e][1], e)
+    return _hint_right(i, data, eids)
+
+
+def _run_c2(steps, env, attach=False, keep_engine=False, config="c2", hints=None, per_step=False, shifted=None):
     """`steps` training steps of the C2 (or `config`) model under `env`; returns the final parameters and whether the plan forked
-    (attach: gradients exchanged over the initialised process group; keep_engine: + the engine's dp_tuned record)."""
+    (attach: gradients exchanged over the initialised process group; keep_engine: + the engine's dp_tuned record).
+    per_step: step i trains on _step_counts(B, G, i) -- every batch of an expert holds other values -- instead of one batch
+    per expert on every step; shifted=<index of an expert>: that expert's steps train on the batch of its PREVIOUS step instead (what
+    a look-ahead that served a stale copy would have trained on)."""
     import bench
     from mmvae_amd import synthetic
 
@@ -146,8 +194,32 @@ def _run_c2(steps, env, attach=False, keep_engine=False, config="c2", hints=None
         B = cfg["batch"]
         eids = list(cfg["experts"].keys())
         data = {eid: (synthetic.synthetic_counts(B, G, seed=77 + i, device=device), synthetic.synthetic_metadata(B, seed=5))
-                for i, (eid, G) in enumerate(cfg["experts"].items())}
-        if hints in ("streamed", "streamed_csr"):
+                for i, (eid, G) in enumerate(cfg["experts"].items())} if not per_step else None
+        meta = synthetic.synthetic_metadata(B, seed=5)
+
+        def cells(i):  # (per-step mode) the cells of step i, on the host
+            e = eids[i % len(eids)]
+            j = i - len(eids) if (shifted is not None and e == eids[shifted] and i >= len(eids)) else i
+            return _step_counts(B, cfg["experts"][e], j)
+
+        if per_step and hints in ("streamed", "streamed_csr"):
+            from mmvae_amd.trainer import Lookahead
+
+            def loader():  # a NEW device tensor every step, as mmvae_amd.data makes them
+                for i in range(steps):
+                    x = cells(i).to(device)
+                    yield (x.to_sparse_csr() if hints == "streamed_csr" else x), meta, eids[i % len(eids)]
+
+            for i, batch in enumerate(Lookahead(loader(), model)):
+                model.training_step(batch, i)
+        elif per_step:
+            xs = [cells(i).to(device) for i in range(steps + 1)]  # resident, every one at an address of its own
+            for i in range(steps):
+                e, e_n = eids[i % len(eids)], eids[(i + 1) % len(eids)]
+                if hints is not None:  # (the hint functions look up "the batch of expert e": this step's and the next one's)
+                    model.hint_next_batch(hints(i, {e_n: (xs[i + 1], meta), e: (xs[i], meta)}, eids))
+                model.training_step((xs[i], meta, e), i)
+        elif hints in ("streamed", "streamed_csr"):
             # a loader that yields a NEW tensor every step (streamed data), wrapped in the trainer's Lookahead
             from mmvae_amd.trainer import Lookahead
 
@@ -194,20 +266,7 @@ def test_pipelined_first_product_is_bit_identical_and_survives_wrong_hints():
     ref, forked = _run_c2(9, {})
     assert forked
 
-    def right(i, data, eids):
-        e = eids[(i + 1) % len(eids)]
-        return (*data[e], e)
-
-    def unreliable(i, data, eids):
-        if i % 4 == 1:
-            return None                                  # no look-ahead for this step
-        if i % 4 == 2:
-            e = eids[i % len(eids)]                      # the same expert again: must not be computed ahead
-            return (*data[e], e)
-        if i % 4 == 3:
-            e = eids[(i + 1) % len(eids)]                # the right expert, another tensor than the one that will arrive
-            return (data[e][0].clone(), data[e][1], e)
-        return right(i, data, eids)
+    right, unreliable = _hint_right, _hint_unreliable
 
     def touched(i, data, eids):
         if i > 0:  # the batch about to be stepped was announced (and its product computed) during the previous step:
@@ -257,6 +316,283 @@ def test_pipelined_first_product_is_bit_identical_and_survives_wrong_hints():
     assert _run_c2.prefetch_stats["consumed"] == 4, _run_c2.prefetch_stats
     bad = [k for k in ref4 if not torch.equal(ref4[k], got4[k])]
     assert not bad, f"c4: {len(bad)} tensors differ, e.g. {bad[:3]}"
+
+
+def _differing(ref, got):
+    return [k for k in ref if not torch.equal(ref[k], got[k])]
+
+
+def test_pipelined_first_product_with_other_cells_on_every_step():
+    """The variants of the test above with DIFFERENT cells on every step (_run_c2, per_step): there every batch of an expert
+    holds the same values on every step, so a step that trained on the previous batch's staged copy, or started from the
+    slabs computed from it, would come out bit-identical and pass.  Reference of every comparison: the same model, seed and
+    batch sequence with MMVAE_PREFETCH=0 and no hints (the program the golden-case tests hold to the reference project);
+    final parameters compared with torch.equal -- the feature's contract is bit-identity, no tolerance.  The control: the
+    hint-free run fed one expert's batches shifted by one (each of its steps trains on its previous batch) must NOT
+    reproduce the reference -- the data does tell the steps apart.  (The control is one more run of the engine on the
+    device, compared on the host: the module path on the CPU is another program and says nothing about these bits.)"""
+    import gc
+
+    def run(*a, **kw):
+        gc.collect()
+        torch.cuda.empty_cache()
+        return _run_c2(*a, per_step=True, **kw)[0]
+
+    off = {"MMVAE_PREFETCH": "0"}
+    ref = run(9, off)
+    assert _differing(ref, run(9, off, shifted=1)), "per-step data: a sequence shifted by one batch trains the same model"
+    for name, hints, want in (("right", _hint_right, lambda st: st["consumed"] == 8 and st["discarded"] == 0),
+                              ("unreliable", _hint_unreliable, lambda st: 0 < st["consumed"] < 8 and st["discarded"] > 0)):
+        got = run(9, {}, hints=hints)
+        st = _run_c2.prefetch_stats
+        assert want(st), (name, st)
+        bad = _differing(ref, got)
+        assert not bad, f"{name}: {len(bad)} tensors differ, e.g. {bad[:3]} ({st})"
+    ref13 = run(13, off)
+    for name in ("streamed", "streamed_csr"):
+        got = run(13, {}, hints=name)
+        st = _run_c2.prefetch_stats
+        assert st["consumed"] == 12 and st["discarded"] == 0 and st["staged_ahead"] == 12, (name, st)
+        assert name != "streamed" or st["plans"] <= 9, st  # (not one per batch)
+        bad = _differing(ref13, got)
+        assert not bad, f"{name}: {len(bad)} tensors differ, e.g. {bad[:3]} ({st})"
+    ref4 = run(5, off, config="c4")
+    got4 = run(5, {}, config="c4", hints=_hint_right)
+    assert _run_c2.prefetch_stats["consumed"] == 4, _run_c2.prefetch_stats
+    bad = _differing(ref4, got4)
+    assert not bad, f"c4: {len(bad)} tensors differ, e.g. {bad[:3]}"
+
+
+class _C2Run:
+    """The C2 model under `env` for a test that drives the loop itself: `with _C2Run(env) as r` gives r.model, r.eids,
+    r.B, r.G, r.device, r.meta; leaving the block CLOSES the engine (also when the body failed) and restores the
+    environment.  r.finish() -> final parameters on the host (+ r.stats, the engine's prefetch_stats and plan count)."""
+
+    def __init__(self, env):
+        self.env = env
+
+    def __enter__(self):
+        import bench
+        from mmvae_amd import rng, synthetic
+
+        self.old = {k: os.environ.get(k) for k in self.env}
+        os.environ.update(self.env)
+        try:
+            cfg = dict(synthetic.CONFIGS["c2"])
+            self.device = torch.device("cuda", 0)
+            self.model = bench.build_model(argparse.Namespace(config="c2", genes="", no_engine=False), cfg, self.device).to(self.device)
+            self.model.train()
+            self.model.trainer.set_stage("training")
+            self.model.optimizers()
+            rng.state(self.device)
+            rng.reseed(1234)
+            self.B, self.eids = cfg["batch"], list(cfg["experts"].keys())
+            self.G = cfg["experts"][self.eids[0]]
+            assert all(g == self.G for g in cfg["experts"].values())
+            self.meta = synthetic.synthetic_metadata(self.B, seed=5)
+        except BaseException:
+            self.__exit__(None, None, None)
+            raise
+        return self
+
+    def finish(self):
+        self.model._flush_engine()
+        torch.cuda.synchronize()
+        eng = self.model._engine
+        self.stats = dict(eng.prefetch_stats, plans=len(eng._plans))
+        return {k: v.detach().cpu().clone() for k, v in self.model.module.state_dict().items()}
+
+    def validate(self, batch):
+        self.model.eval()
+        self.model.trainer.set_stage("validation")
+        with torch.no_grad():
+            self.model.validation_step(batch)
+        self.model.train()
+        self.model.trainer.set_stage("training")
+
+    def __exit__(self, *exc):
+        try:
+            eng = getattr(getattr(self, "model", None), "_engine", None)
+            if eng:
+                torch.cuda.synchronize()
+                eng.close()
+            self.model = None
+        finally:
+            for k, v in self.old.items():
+                os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+        return False
+
+
+def _aliased_passes(hinted, passes, loop="lookahead", validate_between=False, csr=False):
+    """Training passes over ALIASED batches: one persistent device buffer per expert; the loader writes a batch's cells
+    into its expert's buffer and yields torch.from_dlpack(buffer) -- a new tensor object at the same pointer, shape and
+    stride with a version counter of its own at 0: what the caching allocator hands a loop that makes a device tensor per
+    batch, made deterministic.  With two round-robin experts and one batch of look-ahead a buffer is rewritten only after
+    its previous batch has been trained.
+    passes: [(index of the first batch's cells in _rolled_counts, batches the loader holds, batches trained before the
+    loop breaks, index of the expert that opens the pass)].  hinted: look-ahead on (loop="lookahead": mmvae_amd.trainer.Lookahead, the consumer breaks;
+    "manual": a loop that calls hint_next_batch itself and simply stops, withdrawing nothing) or the hint-free reference
+    (MMVAE_PREFETCH=0).  validate_between: a validation step (first expert, cells of its own) between the passes.
+    csr: the batches of the first expert come as CSR tensors (the abandoned one and the one that opens the next pass).
+    Returns (final parameters, prefetch stats)."""
+    import gc
+
+    from mmvae_amd.trainer import Lookahead
+
+    gc.collect()
+    torch.cuda.empty_cache()
+    with _C2Run({} if hinted else {"MMVAE_PREFETCH": "0"}) as r:
+        bufs = {e: torch.empty(r.B, r.G, device=r.device) for e in r.eids}
+        # the aliasing this scenario rests on, on the device: same memory, a version counter of its own that a write
+        # through the base tensor does not move, a new object every time
+        a0 = torch.from_dlpack(bufs[r.eids[0]])
+        bufs[r.eids[0]].fill_(1.0)
+        a1 = torch.from_dlpack(bufs[r.eids[0]])
+        assert a0 is not a1 and a0.data_ptr() == a1.data_ptr() == bufs[r.eids[0]].data_ptr()
+        assert a0._version == 0 and a1._version == 0 and a0.stride() == a1.stride() and a0.shape == a1.shape
+        assert float(a0[0, 0]) == 1.0
+        del a0, a1
+
+        def loader(first, n, opens):
+            for j in range(n):
+                k = (opens + j) % len(r.eids)
+                e = r.eids[k]
+                bufs[e].copy_(_rolled_counts(r.B, r.G, first + j))
+                x = torch.from_dlpack(bufs[e])
+                yield (x.to_sparse_csr() if (csr and k == 0) else x), r.meta, e
+
+        step = 0
+        for p, (first, n, trained, opens) in enumerate(passes):
+            if p and validate_between:
+                r.validate((_rolled_counts(r.B, r.G, 401).to(r.device), r.meta, r.eids[0]))
+            if not hinted:
+                for j, batch in enumerate(loader(first, trained, opens)):
+                    r.model.training_step(batch, step)
+                    step += 1
+            elif loop == "lookahead":
+                for j, batch in enumerate(Lookahead(loader(first, n, opens), r.model)):
+                    if j == trained:
+                        break
+                    r.model.training_step(batch, step)
+                    step += 1
+            else:
+                it = loader(first, n, opens)
+                cur = next(it)
+                for j in range(trained):
+                    nxt = next(it, None)
+                    r.model.hint_next_batch(nxt)
+                    r.model.training_step(cur, step)
+                    step += 1
+                    cur = nxt
+                del cur, nxt, it
+        sd = r.finish()
+        return sd, r.stats
+
+
+def test_lookahead_over_aliased_batches_streams_bit_identically():
+    """Allocator reuse made deterministic (_aliased_passes): 13 streamed steps whose batches are new tensor objects at
+    their expert's one address, with other cells every step.  All 12 announced batches are consumed, none discarded, and
+    the parameters equal the hint-free run's bit for bit."""
+    ref, _ = _aliased_passes(False, [(0, 13, 13, 0)])
+    got, st = _aliased_passes(True, [(0, 13, 13, 0)])
+    assert st["consumed"] == 12 and st["discarded"] == 0, st
+    bad = _differing(ref, got)
+    assert not bad, f"{len(bad)} tensors differ, e.g. {bad[:3]} ({st})"
+
+
+# a pass that announces its third batch (first expert) and stops behind the second; then a pass of three whose first batch
+# is another tensor object at that expert's address, with other cells
+_ABANDON = ((0, 4, 2, 0), (100, 3, 3, 0))
+# the same with ONE step trained: the abandoned batch is the second expert's, which opens the next pass.  That expert has
+# taken no step yet, so its pointer has not been seen under any key: the step that opens the second pass cannot read its
+# batch in place and goes through x_static.<expert>, where the abandoned batch was staged.  (In _ABANDON the first expert's
+# address was seen at the very first step under the same key -- no slabs ahead, same target -- and is read in place.)
+_ABANDON_STAGED = ((0, 4, 1, 0), (100, 3, 3, 1))
+
+
+def test_abandoned_hint_is_never_trained_on():
+    """A batch that was announced -- staged into its expert's static buffer, its first product computed -- and then NOT
+    trained (the loop broke: limit_train_batches, max_steps, an exception), followed by a pass whose first batch is
+    another tensor object at the same address (pointer, shape, stride, version 0: _aliased_passes) with other cells.  The
+    step must train on the cells it was given: parameters equal the hint-free run's bit for bit, and prefetch_stats counts
+    the stale product as discarded (consumed: every other announced batch).
+    lookahead: the consumer breaks out of mmvae_amd.trainer.Lookahead, which withdraws its hint; manual: a loop of its
+    own that just stops -- only the engine's identity check on the PRODUCT stands between the step and the stale slabs
+    (the batch itself is read in place there); manual_staged: that loop stopping where the next pass's first batch must
+    go through the static buffer -- the identity check on the STAGED COPY decides; manual_validate: + a validation step
+    between the passes; manual_csr: the abandoned batch and the one that opens the next pass are CSR tensors (their
+    storage is allocated per batch: address reuse cannot be forced, behaviour only).  Every scenario runs; the failures
+    are reported together."""
+    refs, failures = {}, []
+    for scenario, passes, consumed in (("lookahead", _ABANDON, 3), ("manual", _ABANDON, 3), ("manual_csr", _ABANDON, 3),
+                                       ("manual_staged", _ABANDON_STAGED, 2), ("manual_validate", _ABANDON, 3)):
+        loop = scenario.split("_")[0]
+        kw = dict(validate_between=scenario.endswith("validate"), csr=scenario.endswith("csr"))
+        rk = (passes, kw["validate_between"])  # (CSR batches hold the same cells: the dense reference serves)
+        if rk not in refs:
+            refs = {rk: _aliased_passes(False, passes, validate_between=kw["validate_between"])[0]}
+        got, st = _aliased_passes(True, passes, loop=loop, **kw)
+        bad = _differing(refs[rk], got)
+        if bad:
+            failures.append(f"{scenario}: {len(bad)} tensors differ from the hint-free run, e.g. {bad[:3]} ({st})")
+        if not (st["discarded"] == 1 and st["consumed"] == consumed):
+            failures.append(f"{scenario}: want discarded 1, consumed {consumed}: {st}")
+    assert not failures, "\n".join(failures)
+
+
+def test_programs_stay_bounded_over_a_resident_shuffled_dataset():
+    """A resident dataset of MAX_POINTER_PLANS + 4 batches per expert (other cells in each), look-ahead on: three
+    sequential epochs -- every pointer passes the "seen twice" thresholds of both the current and the announced batch --
+    then two epochs in two different seeded shuffles, modalities alternating throughout.  The number of captured programs
+    is checked after EVERY step (the run stops, and closes its engine, at the first step beyond the bound: dozens of live
+    multi-stream graph executables have crashed the runtime, tests/conftest.py), no program is created in the last
+    shuffled epoch, and the parameters equal the hint-free run's bit for bit."""
+    import gc
+    import random
+
+    from mmvae_amd.engine import MAX_POINTER_PLANS as P
+    from mmvae_amd.trainer import Lookahead
+
+    n_res = P + 4
+
+    def run(hinted):
+        gc.collect()
+        torch.cuda.empty_cache()
+        with _C2Run({} if hinted else {"MMVAE_PREFETCH": "0"}) as r:
+            E = len(r.eids)
+            # A training plan's key is (mode, expert, B, K, explicit, slabs ahead, target, pointer, stride); mode, B, K and
+            # explicit are one value each here.  "slabs ahead" is 0 or the expert's one slab buffer: 2 values.  "target" is
+            # None, the static input buffer of one of the E - 1 other experts, or a caller's pointer; "pointer" is 0 (the
+            # expert's static input buffer) or a caller's pointer.
+            #   keys without a caller's pointer:                      E experts x 2 x (1 + (E - 1))           = 2 E^2
+            #   keys with the current batch's pointer:                at most P by the engine's budget         = P
+            #   keys with a static current batch and a caller's pointer as target: at most P distinct targets are
+            #   read in place, each by the E - 1 other experts' programs, with or without slabs ahead          = 2 (E - 1) P
+            bound = (2 * E - 1) * P + 2 * E * E
+            data = {e: [_rolled_counts(r.B, r.G, E * j + i).to(r.device) for j in range(n_res)] for i, e in enumerate(r.eids)}
+            assert len({x.data_ptr() for xs in data.values() for x in xs}) == E * n_res
+            orders = [{e: list(range(n_res)) for e in r.eids}] * 3
+            orders += [{e: random.Random(seed + i).sample(range(n_res), n_res) for i, e in enumerate(r.eids)} for seed in (11, 23)]
+            assert orders[3] != orders[4] and orders[3] != orders[0]
+            step = created_last = 0
+            for ep, order in enumerate(orders):
+                batches = [(data[e][order[e][j]], r.meta, e) for j in range(n_res) for e in r.eids]
+                before = set(r.model._engine._plans) if r.model._engine else set()
+                for batch in (Lookahead(batches, r.model) if hinted else batches):
+                    r.model.training_step(batch, step)
+                    step += 1
+                    n = len(r.model._engine._plans)
+                    assert n <= bound, f"{n} programs after step {step} (epoch {ep}); bound {bound}"
+                created_last = len(set(r.model._engine._plans) - before)
+            assert created_last == 0, f"{created_last} programs created in the last shuffled epoch"
+            sd = r.finish()
+            return sd, r.stats
+
+    got, st = run(True)
+    assert st["issued"] > 0 and st["consumed"] == st["issued"], st
+    ref, _ = run(False)
+    bad = _differing(ref, got)
+    assert not bad, f"{len(bad)} tensors differ, e.g. {bad[:3]} ({st})"
 
 
 def test_forked_program_is_bit_identical_to_the_single_stream_one():

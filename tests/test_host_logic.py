@@ -415,3 +415,49 @@ def test_lookahead_announces_the_next_batch_and_the_model_consumes_the_hint():
     assert p._next_hint == ("x", "mouse")
     p.hint_next_batch(None)
     assert p._next_hint is None
+    # a consumer that stops early leaves a batch announced that is never trained: the iterator withdraws it -- through
+    # withdraw_hint() where the model has it (the engine then drops what it prepared), else by announcing None
+    for stop in (0, 1):
+        m = Model()
+        for i, b in enumerate(Lookahead(batches, m)):
+            if i == stop:
+                break
+        assert m.seen == [batches[1], None] if stop == 0 else m.seen == [batches[1], batches[2], None], m.seen
+
+    class Withdrawing(Model):
+        withdrawn = 0
+
+        def withdraw_hint(self):
+            self.withdrawn += 1
+
+    m = Withdrawing()
+    for b in Lookahead(batches, m):
+        break
+    assert m.withdrawn == 1 and m.seen == [batches[1]]
+    m = Withdrawing()
+    assert len(list(Lookahead(batches, m))) == 3 and m.withdrawn == 0, "nothing to withdraw behind the last batch"
+
+    def failing():
+        yield batches[0]
+        yield batches[1]
+        raise RuntimeError("loader")
+
+    m = Withdrawing()
+    with pytest.raises(RuntimeError):
+        for b in Lookahead(failing(), m):
+            pass
+    assert m.withdrawn == 1
+    # CMMVAEModel.withdraw_hint: the pending hint goes, and the engine is told (it drops the product and the staged copy)
+    class Engine:
+        calls = 0
+
+        def withdraw_hint(self):
+            self.calls += 1
+
+    p.hint_next_batch(("x", "meta", "mouse"))
+    p.withdraw_hint()  # (no engine yet)
+    assert p._next_hint is None
+    p._engine = Engine()
+    p.hint_next_batch(("x", "meta", "mouse"))
+    p.withdraw_hint()
+    assert p._next_hint is None and p._engine.calls == 1
