@@ -40,7 +40,7 @@ typedef void* mmvae_stream_t; /* hipStream_t */
 /* ABI version: bumped whenever an entry point is added or a signature changes (mmvae_abi_version() returns the
  * value the library was built with; bindings compare it with the header they were written against).
  *   1  round-1 surface (first 20 entry points)      2  end of round 1 (50 entry points)      3+  round 2 */
-#define MMVAE_ABI_VERSION 11
+#define MMVAE_ABI_VERSION 12
 int mmvae_abi_version(void);
 const char* mmvae_build_arch(void);
 
@@ -587,6 +587,36 @@ int mmvae_csr_to_dense_f32(int B, int G, int64_t nnz, const int64_t* crow_indice
  * indices of the scipy slice it is built from (cellxgene_datapipe.py:178-183) -- a third less data on the wire. */
 int mmvae_csr_to_dense_i32_f32(int B, int G, int64_t nnz, const int32_t* crow_indices, const int32_t* col_indices,
                                const float* values, float* out, int64_t ldo, mmvae_stream_t stream);
+
+/* (ABI 12) Rows of a DEVICE-RESIDENT CSR chunk -> one batch: the data feed's device path (mmvae_amd/data.py,
+ * `SpeciesChunks(device_chunks=True)`).  replaces: the per-batch slice of the permuted chunk on the host and its
+ * host-to-device copies (data/local/cellxgene_datapipe.py:169-193) -- the chunk is uploaded once, a batch is one launch.
+ *   chunk    src_crow [n_src_rows + 1], src_col / src_val [src_nnz] (fp32 values; NULL allowed when src_nnz is 0)
+ *   rows     [B] DEVICE int64 row numbers into the chunk, in batch order (may be a slice of the chunk's permutation;
+ *            repeats allowed)
+ *   out_crow [B + 1] the batch's row pointers, ALREADY FILLED by the caller (the host knows every row's length);
+ *   out_col / out_val [out_nnz] are written: row r's segment src[src_crow[rows[r]] ..] -> out[out_crow[r] ..].
+ * One workgroup per output row, coalesced copies, plain vector loads and stores.  Nothing read from memory is used as an
+ * address unchecked: a row number outside [0, n_src_rows) gives an empty row, source offsets are clamped to
+ * [0, src_nnz], destination offsets to [0, out_nnz], and a segment is copied up to the shorter of its source and
+ * destination lengths.  MMVAE_ERR_ARG: NULL pointers, B <= 0, B > 65535, negative counts, counts past 2^31 - 1 with
+ * int32 indices.  The index type (int32 / int64) is that of all four index arrays. */
+int mmvae_csr_gather_rows_i64(int B, int64_t n_src_rows, int64_t src_nnz, const int64_t* src_crow, const int64_t* src_col,
+                              const float* src_val, const int64_t* rows, const int64_t* out_crow, int64_t out_nnz,
+                              int64_t* out_col, float* out_val, mmvae_stream_t stream);
+int mmvae_csr_gather_rows_i32(int B, int64_t n_src_rows, int64_t src_nnz, const int32_t* src_crow, const int32_t* src_col,
+                              const float* src_val, const int64_t* rows, const int32_t* out_crow, int64_t out_nnz,
+                              int32_t* out_col, float* out_val, mmvae_stream_t stream);
+/* The same gather fused with mmvae_csr_to_dense_*: out [B, ldo >= G] fp32 (any ldo) gets the dense rows rows[0 .. B) of
+ * the chunk, without an intermediate CSR batch (`return_dense: true`).  One workgroup per (output row, 8192-column
+ * chunk): zero fill, barrier, scatter.  Row numbers and source offsets are checked as above; column indices outside
+ * [0, G) are dropped.  MMVAE_ERR_ARG additionally for G <= 0 and ldo < G. */
+int mmvae_csr_gather_rows_dense_i64(int B, int G, int64_t n_src_rows, int64_t src_nnz, const int64_t* src_crow,
+                                    const int64_t* src_col, const float* src_val, const int64_t* rows, float* out,
+                                    int64_t ldo, mmvae_stream_t stream);
+int mmvae_csr_gather_rows_dense_i32(int B, int G, int64_t n_src_rows, int64_t src_nnz, const int32_t* src_crow,
+                                    const int32_t* src_col, const float* src_val, const int64_t* rows, float* out,
+                                    int64_t ldo, mmvae_stream_t stream);
 
 /* f1 measurement (NOT on the product path): the first layer's product straight from the CSR batch,
  *   y[B, N] = x_csr[B, G] . W^T (+ bias)      with Wt = W transposed, [G, ldwt >= N], N % 4 == 0, int32 indices.

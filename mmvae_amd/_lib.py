@@ -147,6 +147,10 @@ PROTOTYPES = {
     ),
     "mmvae_csr_to_dense_f32": (_i, [_i, _i, _l, _p, _p, _p, _p, _l, _p]),
     "mmvae_csr_to_dense_i32_f32": (_i, [_i, _i, _l, _p, _p, _p, _p, _l, _p]),
+    "mmvae_csr_gather_rows_i64": (_i, [_i, _l, _l, _p, _p, _p, _p, _p, _l, _p, _p, _p]),
+    "mmvae_csr_gather_rows_i32": (_i, [_i, _l, _l, _p, _p, _p, _p, _p, _l, _p, _p, _p]),
+    "mmvae_csr_gather_rows_dense_i64": (_i, [_i, _i, _l, _l, _p, _p, _p, _p, _p, _l, _p]),
+    "mmvae_csr_gather_rows_dense_i32": (_i, [_i, _i, _l, _l, _p, _p, _p, _p, _p, _l, _p]),
     "mmvae_csr_spmm_wt_i32_f32": (_i, [_i, _i, _i, _l, _p, _p, _p, _p, _l, _p, _p, _l, _p]),
     "mmvae_cond_linear_fwd": (_i, [_i, _i, _i, _p, _l, _p, _p, _p, _p, _p, _p, _l, _p]),
     "mmvae_cond_linear_bwd_dx": (_i, [_i, _i, _i, _p, _l, _p, _p, _p, _p, _p, _l, _i, _p]),

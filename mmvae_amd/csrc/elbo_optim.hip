@@ -1388,6 +1388,132 @@ extern "C" int mmvae_csr_to_dense_i32_f32(int B, int G, int64_t nnz, const int32
     return MMVAE_OK;
 }
 
+// ---- rows of a device-resident CSR chunk -> one batch (the data feed's device path, mmvae_amd/data.py).
+// The batch's row pointers are known on the host before the launch (out_crow, computed per chunk); the kernels only move
+// the rows' (column, value) segments.  Every offset either kernel reads from memory is clamped before it is used as an
+// address, so bad row numbers or malformed row pointers give empty or short rows and never a fault:
+//   src row number outside [0, n_src_rows)  -> empty segment
+//   src offsets                             -> clamped to [0, src_nnz]
+//   dst offsets (gather_rows only)          -> clamped to [0, out_nnz]; min(source length, destination length) is copied
+template <typename I>
+__device__ __forceinline__ void csr_src_segment(int64_t n_src_rows, int64_t src_nnz, const I* __restrict__ src_crow,
+                                                int64_t r, int64_t& beg, int64_t& end) {
+    beg = end = 0;
+    if (r < 0 || r >= n_src_rows) return;
+    beg = (int64_t)src_crow[r];
+    end = (int64_t)src_crow[r + 1];
+    beg = beg < 0 ? 0 : (beg > src_nnz ? src_nnz : beg);
+    end = end < beg ? beg : (end > src_nnz ? src_nnz : end);
+}
+
+// One workgroup per output row: a coalesced copy of the row's column indices and values.
+template <typename I>
+__global__ __launch_bounds__(256) void csr_gather_rows_kernel(int64_t n_src_rows, int64_t src_nnz,
+                                                              const I* __restrict__ src_crow,
+                                                              const I* __restrict__ src_col,
+                                                              const float* __restrict__ src_val,
+                                                              const int64_t* __restrict__ rows,
+                                                              const I* __restrict__ out_crow, int64_t out_nnz,
+                                                              I* __restrict__ out_col, float* __restrict__ out_val) {
+    const int row = blockIdx.x;
+    int64_t sbeg, send;
+    csr_src_segment<I>(n_src_rows, src_nnz, src_crow, rows[row], sbeg, send);
+    int64_t dbeg = (int64_t)out_crow[row], dend = (int64_t)out_crow[row + 1];
+    dbeg = dbeg < 0 ? 0 : (dbeg > out_nnz ? out_nnz : dbeg);
+    dend = dend < dbeg ? dbeg : (dend > out_nnz ? out_nnz : dend);
+    const int64_t n = (send - sbeg) < (dend - dbeg) ? (send - sbeg) : (dend - dbeg);
+    for (int64_t i = threadIdx.x; i < n; i += 256) {
+        out_col[dbeg + i] = src_col[sbeg + i];
+        out_val[dbeg + i] = src_val[sbeg + i];
+    }
+}
+
+// The same indirection fused with csr_to_dense_kernel: one workgroup per (output row, column chunk) zero-fills its
+// chunk of the output row and scatters the source row's elements that fall into it.
+template <typename I>
+__global__ __launch_bounds__(256) void csr_gather_rows_dense_kernel(int G, int64_t n_src_rows, int64_t src_nnz,
+                                                                    const I* __restrict__ src_crow,
+                                                                    const I* __restrict__ src_col,
+                                                                    const float* __restrict__ src_val,
+                                                                    const int64_t* __restrict__ rows,
+                                                                    float* __restrict__ out, int64_t ldo) {
+    const int row = blockIdx.y;
+    const int c0 = blockIdx.x * CSR_CHUNK;
+    const int c1 = min(c0 + CSR_CHUNK, G);
+    float* o = out + (int64_t)row * ldo;
+    const int n4 = (c1 - c0) >> 2;  // 16-byte zero fill (no alignment needed on gfx950)
+    f32x4* o4 = reinterpret_cast<f32x4*>(o + c0);
+    for (int i = threadIdx.x; i < n4; i += 256) o4[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int c = c0 + 4 * n4 + threadIdx.x; c < c1; c += 256) o[c] = 0.f;
+    __syncthreads();
+    int64_t beg, end;
+    csr_src_segment<I>(n_src_rows, src_nnz, src_crow, rows[row], beg, end);
+    for (int64_t i = beg + threadIdx.x; i < end; i += 256) {
+        const int64_t c = (int64_t)src_col[i];
+        if (c >= c0 && c < c1) o[c] = src_val[i];
+    }
+}
+
+template <typename I>
+static int csr_gather_rows_launch(int B, int64_t n_src_rows, int64_t src_nnz, const I* src_crow, const I* src_col,
+                                  const float* src_val, const int64_t* rows, const I* out_crow, int64_t out_nnz,
+                                  I* out_col, float* out_val, mmvae_stream_t stream) {
+    if (B <= 0 || B > 65535 || n_src_rows < 0 || src_nnz < 0 || out_nnz < 0 || !src_crow || !rows || !out_crow)
+        return MMVAE_ERR_ARG;
+    if (src_nnz > 0 && (!src_col || !src_val)) return MMVAE_ERR_ARG;
+    if (out_nnz > 0 && (!out_col || !out_val)) return MMVAE_ERR_ARG;
+    if (sizeof(I) == 4 && (src_nnz > 0x7fffffffLL || out_nnz > 0x7fffffffLL)) return MMVAE_ERR_ARG;
+    if (out_nnz == 0 || src_nnz == 0) return MMVAE_OK;  // nothing to copy
+    MMVAE_LAUNCH(csr_gather_rows_kernel<I>, dim3(B), dim3(256), 0, (hipStream_t)stream, n_src_rows, src_nnz, src_crow,
+                 src_col, src_val, rows, out_crow, out_nnz, out_col, out_val);
+    MMVAE_LAUNCH_CHECK();
+    return MMVAE_OK;
+}
+
+template <typename I>
+static int csr_gather_rows_dense_launch(int B, int G, int64_t n_src_rows, int64_t src_nnz, const I* src_crow,
+                                        const I* src_col, const float* src_val, const int64_t* rows, float* out,
+                                        int64_t ldo, mmvae_stream_t stream) {
+    if (B <= 0 || B > 65535 || G <= 0 || n_src_rows < 0 || src_nnz < 0 || !src_crow || !rows || !out || ldo < G)
+        return MMVAE_ERR_ARG;
+    if (src_nnz > 0 && (!src_col || !src_val)) return MMVAE_ERR_ARG;
+    if (sizeof(I) == 4 && src_nnz > 0x7fffffffLL) return MMVAE_ERR_ARG;
+    MMVAE_LAUNCH(csr_gather_rows_dense_kernel<I>, dim3(ceil_div_i(G, CSR_CHUNK), B), dim3(256), 0, (hipStream_t)stream,
+                 G, n_src_rows, src_nnz, src_crow, src_col, src_val, rows, out, ldo);
+    MMVAE_LAUNCH_CHECK();
+    return MMVAE_OK;
+}
+
+extern "C" int mmvae_csr_gather_rows_i64(int B, int64_t n_src_rows, int64_t src_nnz, const int64_t* src_crow,
+                                         const int64_t* src_col, const float* src_val, const int64_t* rows,
+                                         const int64_t* out_crow, int64_t out_nnz, int64_t* out_col, float* out_val,
+                                         mmvae_stream_t stream) {
+    return csr_gather_rows_launch<int64_t>(B, n_src_rows, src_nnz, src_crow, src_col, src_val, rows, out_crow, out_nnz,
+                                           out_col, out_val, stream);
+}
+
+extern "C" int mmvae_csr_gather_rows_i32(int B, int64_t n_src_rows, int64_t src_nnz, const int32_t* src_crow,
+                                         const int32_t* src_col, const float* src_val, const int64_t* rows,
+                                         const int32_t* out_crow, int64_t out_nnz, int32_t* out_col, float* out_val,
+                                         mmvae_stream_t stream) {
+    return csr_gather_rows_launch<int32_t>(B, n_src_rows, src_nnz, src_crow, src_col, src_val, rows, out_crow, out_nnz,
+                                           out_col, out_val, stream);
+}
+
+extern "C" int mmvae_csr_gather_rows_dense_i64(int B, int G, int64_t n_src_rows, int64_t src_nnz,
+                                               const int64_t* src_crow, const int64_t* src_col, const float* src_val,
+                                               const int64_t* rows, float* out, int64_t ldo, mmvae_stream_t stream) {
+    return csr_gather_rows_dense_launch<int64_t>(B, G, n_src_rows, src_nnz, src_crow, src_col, src_val, rows, out, ldo,
+                                                 stream);
+}
+
+extern "C" int mmvae_csr_gather_rows_dense_i32(int B, int G, int64_t n_src_rows, int64_t src_nnz,
+                                               const int32_t* src_crow, const int32_t* src_col, const float* src_val,
+                                               const int64_t* rows, float* out, int64_t ldo, mmvae_stream_t stream) {
+    return csr_gather_rows_dense_launch<int32_t>(B, G, n_src_rows, src_nnz, src_crow, src_col, src_val, rows, out, ldo,
+                                                 stream);
+}
+
 // ---- f1 experiment: CSR x dense^T product of the first layer WITHOUT densifying.
 // y[b, :] = sum over the stored elements (g, v) of row b of v * Wt[g, :]  (+ bias), Wt = the layer's weight TRANSPOSED
 // ([G, N], N contiguous: a stored element then touches one contiguous 4 N-byte row of Wt).  One workgroup per cell row

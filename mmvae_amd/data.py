@@ -14,6 +14,14 @@ numpy state) so that an epoch is reproducible and data-parallel ranks can be giv
 streams; the next chunk is loaded and permuted by a background thread while the current one is consumed; batches can be
 staged to the device as CSR components from pinned memory (12 B per stored element instead of 4 B per gene), where
 `mmvae_csr_to_dense_f32` densifies them straight into the step's input buffer.
+
+Device-resident chunks (`SpeciesChunks(device_chunks=True)`, opt-in): instead of gathering every batch on the host and
+copying it over, the background chunk thread uploads each chunk ONCE -- its CSR arrays, its row order and the row-pointer
+table of every batch it will yield (`batch_row_pointers`), validated on the host first (`validate_csr_chunk`) -- and a
+batch is one launch of `mmvae_csr_gather_rows_*` (or `mmvae_csr_gather_rows_dense_*` with `return_dense`) that copies
+the chosen rows out of the resident chunk.  Per batch the host is left with that launch and the metadata slice.  The
+batches are the same, bit for bit, as those of the host path; at most two chunks are resident (the one being consumed
+and the next), and a chunk over `device_chunk_bytes` takes the host path for that chunk alone.
 """
 from __future__ import annotations
 
@@ -23,6 +31,7 @@ import os
 import pickle
 import queue
 import threading
+import warnings
 from typing import Iterator, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -134,6 +143,56 @@ def feed_lib():
                                "make -C mmvae_amd/csrc")
         _FEED = lib
     return _FEED
+
+
+def validate_csr_chunk(indptr: np.ndarray, indices: np.ndarray, data: np.ndarray, n_cols: int, where: str) -> None:
+    """The host-side check of a chunk that is about to become device-resident: raises ValueError (naming `where`, the
+    chunk's file) unless the row pointers start at 0, never decrease and end at the number of stored elements, and every
+    column index lies in [0, n_cols).  The gather kernels clamp what they read anyway; this is what makes a malformed
+    file an error instead of silently shortened rows."""
+    if indptr.ndim != 1 or len(indptr) < 1 or int(indptr[0]) != 0:
+        raise ValueError(f"{where}: malformed CSR chunk: indptr[0] != 0")
+    if len(indptr) > 1 and bool((indptr[1:] < indptr[:-1]).any()):
+        raise ValueError(f"{where}: malformed CSR chunk: indptr decreases")
+    if not (int(indptr[-1]) == len(indices) == len(data)):
+        raise ValueError(f"{where}: malformed CSR chunk: indptr[-1] = {int(indptr[-1])} but {len(indices)} indices and "
+                         f"{len(data)} values")
+    if len(indices) and (int(indices.min()) < 0 or int(indices.max()) >= n_cols):
+        raise ValueError(f"{where}: malformed CSR chunk: column index outside [0, {n_cols})")
+
+
+def batch_row_pointers(indptr: np.ndarray, order: np.ndarray, batch_size: int, allow_partials: bool = False,
+                       dtype=np.int32) -> Tuple[np.ndarray, List[int], List[int]]:
+    """Row pointers of EVERY batch a chunk yields, in one vectorised pass: batch k is rows order[k B : (k + 1) B] of the
+    chunk, and its `crow_indices` are the running sum of those rows' lengths.  Returns (table, nnz, n_rows): `table`
+    is [n_batches, B + 1] of `dtype`, nnz[k] / n_rows[k] are Python ints.  A partial last batch -- kept only with
+    `allow_partials` -- has n_rows < B: its row pointers are table[k, :n_rows + 1] (the padding repeats its nnz)."""
+    B = int(batch_size)
+    n = len(order)
+    n_batches = -(-n // B) if allow_partials else n // B
+    lengths = np.zeros(n_batches * B, dtype=np.int64)
+    kept = min(n, n_batches * B)
+    row_len = np.diff(np.asarray(indptr).astype(np.int64, copy=False))
+    lengths[:kept] = row_len[np.asarray(order[:kept], dtype=np.int64)]
+    table = np.zeros((n_batches, B + 1), dtype=np.int64)
+    np.cumsum(lengths.reshape(n_batches, B), axis=1, out=table[:, 1:])
+    nnz = [int(v) for v in table[:, B]]
+    n_rows = [min(B, n - k * B) for k in range(n_batches)]
+    if n_batches and nnz and max(nnz) > np.iinfo(dtype).max:
+        raise ValueError(f"a batch of {max(nnz)} stored elements needs index_dtype=torch.int64")
+    return table.astype(dtype, copy=False), nnz, n_rows
+
+
+class _DeviceChunk:
+    """One chunk resident on the device: a `torch.sparse_csr` view of it, its row order (int64) and the row-pointer table
+    of its batches, all parts of ONE buffer uploaded by one copy on the feed's copy stream; `event` is recorded behind
+    that copy.  The metadata frame and the host copy of the row order stay on the host (the metadata slice)."""
+    __slots__ = ("buf", "csr", "rows", "table", "nnz", "n_rows", "event", "metadata", "order", "ready")
+
+    def __init__(self, buf, csr, rows, table, nnz, n_rows, event, metadata, order):
+        self.buf, self.csr, self.rows, self.table, self.nnz, self.n_rows = buf, csr, rows, table, nnz, n_rows
+        self.event, self.metadata, self.order = event, metadata, order
+        self.ready = None  # handle of the producing stream once it waits for `event` (first batch of the chunk)
 
 
 class _Slot:
@@ -249,12 +308,18 @@ class SpeciesChunks:
     the epoch's kept batches (across chunks, dropped partial batches not counted) are dealt out in rounds of `world`,
     rank r takes the r-th batch of every COMPLETE round and the incomplete last round is dropped, so every rank yields
     exactly floor(n_batches / world) batches of the same modality schedule -- a rank that ran short would leave the
-    others blocked in the gradient all-reduce (the reference has no distributed sampler)."""
+    others blocked in the gradient all-reduce (the reference has no distributed sampler).
+
+    `device_chunks=True` (needs a GPU `device`): chunks are uploaded once and batches gathered on the device by one HIP
+    launch each (`_iter_device`); same batches.  `device_chunk_bytes`: budget of one resident chunk (default: a quarter
+    of the free device memory when the iterator starts); at most two chunks are resident, a chunk over the budget is
+    gathered on the host (one warning per object)."""
 
     def __init__(self, directory_path: str, npz_masks, metadata_masks, batch_size: int, name: str,
                  allow_partials: bool = False, shuffle: bool = True, return_dense: bool = False, seed: int = 0,
                  device: Optional[Union[str, torch.device]] = None, prefetch: bool = True, rank: int = 0, world: int = 1,
-                 workers: int = 3, gather_threads: int = 2, index_dtype: torch.dtype = torch.int32):
+                 workers: int = 3, gather_threads: int = 2, index_dtype: torch.dtype = torch.int32,
+                 device_chunks: bool = False, device_chunk_bytes: Optional[int] = None):
         self.chunks = list_chunks(directory_path, npz_masks, metadata_masks)
         self.batch_size = int(batch_size)
         self.name = name
@@ -274,6 +339,14 @@ class SpeciesChunks:
         self.index_dtype = index_dtype
         self.epoch = 0
         self._slots: List[_Slot] = []
+        # device-resident chunks (opt-in): see _iter_device
+        self.device_chunks = bool(device_chunks)
+        if self.device_chunks and (self.device is None or self.device.type != "cuda"):
+            raise ValueError("device_chunks=True needs a GPU device (device='cuda'): the chunks live in device memory")
+        if device_chunk_bytes is not None and int(device_chunk_bytes) < 0:
+            raise ValueError("device_chunk_bytes must not be negative")
+        self.device_chunk_bytes = None if device_chunk_bytes is None else int(device_chunk_bytes)
+        self._warned_budget = False
 
     # ---- chunks: (scipy CSR over the mapped file, metadata, row order)
     def _prepared_chunks(self, rng: np.random.Generator) -> Iterator:
@@ -376,6 +449,9 @@ class SpeciesChunks:
     def __iter__(self) -> Iterator[Tuple[torch.Tensor, pd.DataFrame, str]]:
         from collections import deque
 
+        if self.device_chunks:
+            yield from self._iter_device()
+            return
         rng = np.random.default_rng([self.seed, self.epoch])
         self.epoch += 1
         chunks = self._prepared_chunks(rng)
@@ -425,6 +501,173 @@ class SpeciesChunks:
                 inflight.append((pool.submit(self._gather, slot, matrix, rows), matrix, metadata, rows))
             while inflight:
                 yield finish()
+
+    # ---- device-resident chunks: one upload per chunk (chunk thread), one gather launch per batch (consumer thread)
+    @staticmethod
+    def _pad16(n: int) -> int:
+        return (n + 15) // 16 * 16
+
+    def _chunk_bytes(self, n_rows: int, nnz: int, n_batches: int) -> int:
+        """Device bytes of a resident chunk: row pointers, column indices, values, row order and the batches' table."""
+        isz = 4 if self.index_dtype == torch.int32 else 8
+        return (self._pad16((n_rows + 1) * isz) + self._pad16(nnz * isz) + self._pad16(nnz * 4) + self._pad16(n_rows * 8)
+                + self._pad16(n_batches * (self.batch_size + 1) * isz))
+
+    def _upload_chunk(self, matrix, metadata, order: np.ndarray, where: str, stream, staging: dict) -> _DeviceChunk:
+        """Canonical fp32 CSR in `index_dtype`, checked on the host, packed into page-locked staging and sent to the device
+        by two non-blocking copies on `stream` (the chunk's arrays + row order; the small table of its batches, which the
+        batches' `crow_indices` are views of and which therefore lives as long as the last of them)."""
+        n, G = matrix.shape
+        nnz = len(matrix.indices)
+        if self.index_dtype == torch.int32 and (G > 0x7fffffff or nnz > 0x7fffffff):
+            raise ValueError(f"{where}: a chunk with more than 2^31 - 1 columns or stored elements needs "
+                             "index_dtype=torch.int64")
+        validate_csr_chunk(matrix.indptr, matrix.indices, matrix.data, G, where)
+        np_idx = np.int32 if self.index_dtype == torch.int32 else np.int64
+        table, nnzs, n_rows = batch_row_pointers(matrix.indptr, order, self.batch_size, self.allow_partials, np_idx)
+        isz = np.dtype(np_idx).itemsize
+        parts = [(matrix.indptr, np_idx, self.index_dtype), (matrix.indices, np_idx, self.index_dtype),
+                 (matrix.data, np.float32, torch.float32), (order, np.int64, torch.int64),
+                 (table.reshape(-1), np_idx, self.index_dtype)]
+        offsets, total = [], 0
+        for src, np_dtype, _ in parts:
+            offsets.append(total)
+            total += self._pad16(len(src) * np.dtype(np_dtype).itemsize)
+        o_table = offsets[-1]
+        if staging.get("event") is not None:  # the copies that read the staging buffer (last chunk's) must be done
+            staging["event"].synchronize()
+            staging["event"] = None
+        if staging.get("buf") is None or staging["buf"].numel() < total:
+            staging["buf"] = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        host = staging["buf"].numpy()
+        for (src, np_dtype, _), o in zip(parts, offsets):
+            nb = len(src) * np.dtype(np_dtype).itemsize
+            np.copyto(host[o:o + nb].view(np_dtype), src, casting="unsafe")  # (ranges checked above)
+        with torch.cuda.device(self.device), torch.cuda.stream(stream):
+            buf = torch.empty(max(o_table, 16), dtype=torch.uint8, device=self.device)
+            tbuf = torch.empty(max(total - o_table, 16), dtype=torch.uint8, device=self.device)
+            if o_table:
+                buf[:o_table].copy_(staging["buf"][:o_table], non_blocking=True)
+            if total > o_table:
+                tbuf[:total - o_table].copy_(staging["buf"][o_table:total], non_blocking=True)
+            dev = []
+            for (src, np_dtype, t_dtype), o in zip(parts[:4], offsets[:4]):
+                dev.append(buf[o:o + len(src) * np.dtype(np_dtype).itemsize].view(t_dtype))
+            csr = torch.sparse_csr_tensor(dev[0], dev[1], dev[2], size=(n, G))
+            tab = tbuf[:table.size * isz].view(self.index_dtype).view(table.shape[0], self.batch_size + 1)
+            event = torch.cuda.Event()
+            event.record(stream)
+        staging["event"] = event
+        return _DeviceChunk((buf, tbuf), csr, dev[3], tab, nnzs, n_rows, event, metadata, order)
+
+    def _device_chunks(self, rng: np.random.Generator, budget: int, resident: threading.Semaphore,
+                       stop: threading.Event) -> Iterator:
+        """`_prepared_chunks` (same generator calls in the same order) whose chunks go to the device as they are loaded:
+        yields `_DeviceChunk`s, or `(matrix, metadata, rows)` for a chunk over the budget (host path for that chunk).
+        Holds one of the two `resident` permits per uploaded chunk; the consumer gives it back when it is done with it."""
+        order = list(range(len(self.chunks)))
+        if self.shuffle:
+            order = [int(i) for i in rng.permutation(len(order))]
+        stream = torch.cuda.Stream(device=self.device)
+        staging: dict = {}
+        for ci in order:
+            where = self.chunks[ci][0]
+            matrix, metadata = load_chunk(*self.chunks[ci])
+            n = matrix.shape[0]
+            rows = (rng.permutation(n) if self.shuffle else np.arange(n)).astype(np.int64)
+            n_batches = -(-n // self.batch_size) if self.allow_partials else n // self.batch_size
+            if n_batches == 0:
+                continue
+            need = self._chunk_bytes(n, len(matrix.indices), n_batches)
+            if need > budget:
+                if not self._warned_budget:
+                    self._warned_budget = True
+                    warnings.warn(f"{where}: the chunk needs {need} bytes of device memory, over device_chunk_bytes = "
+                                  f"{budget}: chunks over the budget are gathered on the host", RuntimeWarning)
+                yield matrix, metadata, rows
+                continue
+            while not resident.acquire(timeout=0.1):
+                if stop.is_set():
+                    return
+            yield self._upload_chunk(matrix, metadata, rows, where, stream, staging)
+        if staging.get("event") is not None:
+            staging["event"].synchronize()
+
+    def _device_batch(self, ch: _DeviceChunk, k: int):
+        """Batch k of a resident chunk: one gather launch on the current (producing) stream + the metadata slice."""
+        from . import ops
+
+        cur = torch.cuda.current_stream(self.device)
+        if ch.ready != cur.cuda_stream:  # once per chunk: behind the upload; the chunk must outlive this stream's gathers
+            cur.wait_event(ch.event)
+            for b in ch.buf:
+                b.record_stream(cur)
+            ch.ready = cur.cuda_stream
+        B, n_rows = self.batch_size, ch.n_rows[k]
+        rows = ch.rows[k * B:k * B + n_rows]
+        if self.return_dense:
+            x = ops.csr_gather_rows_dense(ch.csr, rows)
+        else:
+            x = ops.csr_gather_rows(ch.csr, rows, ch.table[k, :n_rows + 1], ch.nnz[k])
+        md = ch.metadata.take(ch.order[k * B:k * B + n_rows])
+        md.index = pd.RangeIndex(len(md))
+        return x, md, self.name
+
+    def _host_batch(self, slots: list, matrix, metadata, rows: np.ndarray):
+        """One batch of a chunk over the device budget: the host gather and staging of `__iter__`, made in line."""
+        slot = slots.pop(0)
+        slots.append(slot)
+        if slot.event is not None:
+            slot.event.synchronize()
+            slot.event = None
+        slot, nnz, n_rows = self._gather(slot, matrix, rows)
+        x = self._tensor(slot, nnz, n_rows, matrix.shape[1])
+        md = metadata.take(rows)
+        md.index = pd.RangeIndex(len(md))
+        return x, md, self.name
+
+    def _iter_device(self) -> Iterator[Tuple[torch.Tensor, pd.DataFrame, str]]:
+        """`__iter__` with device-resident chunks.  Same chunk order, row orders, batches and dealing among ranks; the
+        batch dealt to this rank is gathered when its turn comes and handed out once its round of `world` is complete."""
+        rng = np.random.default_rng([self.seed, self.epoch])
+        self.epoch += 1
+        budget = self.device_chunk_bytes
+        if budget is None:
+            budget = torch.cuda.mem_get_info(self.device)[0] // 4
+        resident, stop = threading.Semaphore(2), threading.Event()
+        chunks = self._device_chunks(rng, budget, resident, stop)
+        if self.prefetch:
+            chunks = self._background(chunks)
+        slots: list = []
+        dealt, mine = 0, None
+        B = self.batch_size
+        try:
+            for item in chunks:
+                ch = item if isinstance(item, _DeviceChunk) else None
+                if ch is None:
+                    matrix, metadata, order = item
+                    if not slots:
+                        slots = [_Slot(B, True, self.index_dtype) for _ in range(2)]
+                    n = matrix.shape[0]
+                    starts = [i for i in range(0, n, B) if i + B <= n or self.allow_partials]
+                item = None
+                try:
+                    for k in (range(len(ch.nnz)) if ch is not None else range(len(starts))):
+                        if dealt == self.rank:
+                            mine = (self._device_batch(ch, k) if ch is not None
+                                    else self._host_batch(slots, matrix, metadata, order[starts[k]:starts[k] + B]))
+                        dealt += 1
+                        if dealt == self.world:
+                            dealt = 0
+                            out, mine = mine, None
+                            yield out
+                finally:
+                    if ch is not None:
+                        ch = None
+                        resident.release()
+        finally:
+            stop.set()
+            chunks.close()
 
     def __len__(self) -> int:
         raise TypeError("SpeciesChunks streams chunk files: its length is not known without reading them")

@@ -734,6 +734,65 @@ def csr_to_dense(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.T
     return out
 
 
+def _csr_chunk(chunk: torch.Tensor, rows: torch.Tensor, what: str):
+    """(crow, col, val, n_src_rows, G, src_nnz, B) of a device-resident CSR chunk and a row list, checked."""
+    if chunk.layout != torch.sparse_csr or chunk.dim() != 2:
+        raise ValueError(f"{what}: expected a 2-D torch.sparse_csr chunk")
+    crow, col, val = chunk.crow_indices(), chunk.col_indices(), chunk.values()
+    if not val.is_cuda or not rows.is_cuda:
+        raise _lib.HipLibraryError(f"{what}: CPU tensors have no HIP path")
+    if crow.dtype != col.dtype or crow.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{what}: the chunk's index arrays must both be int32 or both int64")
+    if val.dtype != torch.float32:
+        raise TypeError(f"{what}: expected fp32 values, got {val.dtype}")
+    if rows.dtype != torch.int64 or rows.dim() != 1 or not rows.is_contiguous():
+        raise TypeError(f"{what}: rows must be a contiguous 1-D int64 tensor")
+    if not (crow.is_contiguous() and col.is_contiguous() and val.is_contiguous()):
+        raise ValueError(f"{what}: the chunk's arrays must be contiguous")
+    return crow, col, val, int(chunk.shape[0]), int(chunk.shape[1]), int(val.numel()), int(rows.numel())
+
+
+def csr_gather_rows(chunk: torch.Tensor, rows: torch.Tensor, out_crow: torch.Tensor, nnz: int) -> torch.Tensor:
+    """Rows `rows` (device int64, in batch order) of a device-resident `torch.sparse_csr` chunk as a new
+    `torch.sparse_csr` batch: one HIP launch copies the rows' column indices and values.  `out_crow` [len(rows) + 1]
+    holds the batch's row pointers already (index dtype of the chunk; the caller knows the row lengths) and becomes the
+    batch's `crow_indices`; `nnz` is its last entry, known on the host."""
+    lib = _lib.load()
+    crow, col, val, n_src, G, src_nnz, B = _csr_chunk(chunk, rows, "csr_gather_rows")
+    if not out_crow.is_cuda:
+        raise _lib.HipLibraryError("csr_gather_rows: CPU tensors have no HIP path")
+    if out_crow.dtype != crow.dtype or out_crow.dim() != 1 or out_crow.numel() != B + 1 or not out_crow.is_contiguous():
+        raise ValueError(f"csr_gather_rows: out_crow must be a contiguous {crow.dtype} vector of {B + 1} row pointers")
+    nnz = int(nnz)
+    if nnz < 0:
+        raise ValueError("csr_gather_rows: negative nnz")
+    out_col = torch.empty(nnz, dtype=col.dtype, device=val.device)
+    out_val = torch.empty(nnz, dtype=torch.float32, device=val.device)
+    fn = lib.mmvae_csr_gather_rows_i32 if crow.dtype == torch.int32 else lib.mmvae_csr_gather_rows_i64
+    _lib.check(fn(B, n_src, src_nnz, crow.data_ptr(), col.data_ptr() if src_nnz else None,
+                  val.data_ptr() if src_nnz else None, rows.data_ptr(), out_crow.data_ptr(), nnz,
+                  out_col.data_ptr() if nnz else None, out_val.data_ptr() if nnz else None, _stream()),
+               "mmvae_csr_gather_rows")
+    return torch.sparse_csr_tensor(out_crow, out_col, out_val, size=(B, G))
+
+
+def csr_gather_rows_dense(chunk: torch.Tensor, rows: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Dense fp32 [len(rows), G] rows `rows` (device int64) of a device-resident `torch.sparse_csr` chunk: the gather
+    and the densify pass as one HIP launch, no intermediate CSR batch."""
+    lib = _lib.load()
+    crow, col, val, n_src, G, src_nnz, B = _csr_chunk(chunk, rows, "csr_gather_rows_dense")
+    if out is None:
+        out = torch.empty((B, G), dtype=torch.float32, device=val.device)
+    _chk(out, "out")
+    if tuple(out.shape) != (B, G):
+        raise ValueError(f"out {tuple(out.shape)} != {(B, G)}")
+    fn = lib.mmvae_csr_gather_rows_dense_i32 if crow.dtype == torch.int32 else lib.mmvae_csr_gather_rows_dense_i64
+    _lib.check(fn(B, G, n_src, src_nnz, crow.data_ptr(), col.data_ptr() if src_nnz else None,
+                  val.data_ptr() if src_nnz else None, rows.data_ptr(), _ptr(out), _mat(out, "out")[2], _stream()),
+               "mmvae_csr_gather_rows_dense")
+    return out
+
+
 def csr_spmm_wt(x: torch.Tensor, wt: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """f1 measurement: y[B, N] = x_csr[B, G] . wt[G, N] (+ bias) straight from a `torch.sparse_csr` batch with int32
     indices; wt is the layer's weight TRANSPOSED.  Not on the product path (the engine densifies)."""
