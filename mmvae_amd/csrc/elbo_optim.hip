@@ -135,9 +135,10 @@ __global__ __launch_bounds__(256) void elbo_rows_kernel(int B, int K, int T, con
     float v = (lane < K) ? -se_s[wv][lane] : -INFINITY;
     const float mx = wave_max(v);
     const float ex = (lane < K) ? expf(v - mx) : 0.f;
-    const float lse = mx + logf(wave_sum(ex));
+    const float sum = wave_sum(ex);
+    const float lse = mx + logf(sum);  // for the bound only: at SE ~ 1e4 its fp32 ulp is ~1e-3, too coarse for w
     if (lane == 0) recon_row[b] = -(lse - logf((float)K));
-    if (w_out && lane < K) w_out[(int64_t)lane * B + b] = expf(v - lse);
+    if (w_out && lane < K) w_out[(int64_t)lane * B + b] = ex / sum;
 }
 
 // ---- opt-in "full IWAE" objective of the K-sample extension (not in the reference).
@@ -181,8 +182,9 @@ __global__ __launch_bounds__(256) void elbo_rows_iwae_kernel(int B, int K, int T
     const float v = (lane < K) ? -se - c * r : -INFINITY;
     const float mx = wave_max(v);
     const float ex = (lane < K) ? expf(v - mx) : 0.f;
-    const float lse = mx + logf(wave_sum(ex));
-    const float w = (lane < K) ? expf(v - lse) : 0.f;
+    const float sum = wave_sum(ex);
+    const float lse = mx + logf(sum);  // for the bound only (see elbo_rows_kernel)
+    const float w = ex / sum;          // ex is 0 on the lanes past K
     const float wse = wave_sum(w * se), wr = wave_sum(w * r);
     if (lane == 0) {
         rows3[b] = -(lse - logf((float)K));

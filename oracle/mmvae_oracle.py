@@ -330,6 +330,14 @@ def model_forward(spec: ModelSpec, sd, x, expert_id: str, eps, training: bool, m
     return {"mu": mu, "std": std, "z": z, "xhat": xhat, "hidden": hidden, "shared_xhat": sh}
 
 
+def _logsumexp0(v):
+    """logsumexp over dim 0 whose gradient is exp(v - max) / sum.  torch.logsumexp's backward is exp(v - result): in fp32,
+    with |v| ~ 1e4 (squared error of a cell of 20 000 genes), `result` carries an ulp of ~1e-3 and every weight of the cell
+    is off by one common factor of up to 5e-4 -- the oracle would then hold the K-sample gradients to its own rounding."""
+    mx = v.max(dim=0).values.detach()
+    return mx + torch.log(torch.exp(v - mx).sum(dim=0))
+
+
 def elbo_iwae(mu, std, x, xhat, kl_weight: float, K: int, eps, z):
     """Opt-in "full IWAE" mode of the K-sample extension (not in the reference, parity unpinned): the
     analytic KL is replaced by the sampled log-density ratio inside the log-mean-exp,
@@ -343,7 +351,7 @@ def elbo_iwae(mu, std, x, xhat, kl_weight: float, K: int, eps, z):
     zk = z.reshape(K, B, -1)
     r = (-std.log().unsqueeze(0) - 0.5 * epsk.pow(2) + 0.5 * zk.pow(2)).sum(-1)  # [K,B]
     lw = -se - (kl_weight / B) * r
-    loss = (-(torch.logsumexp(lw, dim=0) - torch.log(torch.tensor(float(K))))).sum()
+    loss = (-(_logsumexp0(lw) - torch.log(torch.tensor(float(K))))).sum()
     w = torch.softmax(lw, dim=0).detach()
     return {"loss": loss, "recon_loss": (w * se).sum().detach(), "kl_loss": ((w * r).sum() / B).detach(),
             "kl_weight": kl_weight}
@@ -360,7 +368,7 @@ def elbo(mu, std, x, xhat, kl_weight: float, K: int = 1):
     else:
         B = x.shape[0]
         se = ((xhat.reshape(K, B, -1) - x.unsqueeze(0)) ** 2).sum(-1)  # [K,B]
-        recon = (-(torch.logsumexp(-se, dim=0) - torch.log(torch.tensor(float(K))))).sum()
+        recon = (-(_logsumexp0(-se) - torch.log(torch.tensor(float(K))))).sum()
     return {"loss": recon + kl_weight * kl, "recon_loss": recon, "kl_loss": kl, "kl_weight": kl_weight}
 
 
