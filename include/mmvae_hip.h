@@ -40,7 +40,7 @@ typedef void* mmvae_stream_t; /* hipStream_t */
 /* ABI version: bumped whenever an entry point is added or a signature changes (mmvae_abi_version() returns the
  * value the library was built with; bindings compare it with the header they were written against).
  *   1  round-1 surface (first 20 entry points)      2  end of round 1 (50 entry points)      3+  round 2 */
-#define MMVAE_ABI_VERSION 12
+#define MMVAE_ABI_VERSION 13
 int mmvae_abi_version(void);
 const char* mmvae_build_arch(void);
 
@@ -338,6 +338,9 @@ int mmvae_sum_rows_f32(int H, int64_t n, const float* v, int64_t ld, float* out_
  *                      state[5] = cv > 0 (written by the caller; mmvae_adam_prepare never touches it): clip BY VALUE --
  *                      GradientClipConfig(algorithm="value"), config.py:8, Lightning clip_gradients ->
  *                      clip_grad_value_ -- g = clamp(clip*grad_scale*grad, -cv, cv) + wd*p (pass max_norm = 0: clip = 1).
+ * mmvae_adam_step_hp (and the other `_hp` entries below): the same passes with lr, weight decay and the decay mode read
+ *                      from device words (`hyper`) -- what a captured program launches, so that a learning-rate
+ *                      schedule is one small write per step; decoupled mode = torch.optim.AdamW.
  * ------------------------------------------------------------------------------------------------------------ */
 #define MMVAE_ADAM_STATE_FLOATS 8
 #define MMVAE_PREPARE_NORM 1u
@@ -347,7 +350,7 @@ int mmvae_grad_sqnorm(int64_t n, const float* grad, float* partials, mmvae_strea
 int mmvae_adam_prepare(int64_t n_partials, const float* partials, float max_norm, float grad_scale, float beta1,
                        float beta2, float* state, unsigned flags, mmvae_stream_t stream);
 /* Host-side launch state (like mmvae_gemm_set_workgroup_cap): workgroups > 0 confines mmvae_adam_step /
- * mmvae_adam_step_copy to that many compute units (1024-thread workgroups, one per CU) for callers that run the update
+ * mmvae_adam_step_copy (and their _hp siblings) to that many compute units (1024-thread workgroups, one per CU) for callers that run the update
  * beside a kernel of another stream whose grid is capped to the remaining units; 0 = the chip-filling grid.
  * Elementwise work: results do not depend on it.  Replaces nothing in the reference (torch.optim.Adam.step,
  * cmmvae_model.py:203-213, is stream-ordered behind backward). */
@@ -370,6 +373,21 @@ int mmvae_grad_sqnorm_ranges_prepare(int n_ranges, const float* const* grads, co
 int mmvae_adam_step(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const float* state,
                     float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                     mmvae_stream_t stream);
+/* (ABI 13) The same passes with the learning rate, the weight decay and the decay mode read from DEVICE memory, so that
+ * a captured program follows a learning-rate schedule (one small write per step) instead of holding them as constants.
+ * `hyper`: MMVAE_ADAM_HYPER_FLOATS floats per optimiser -- hyper[0] = lr, hyper[1] = weight_decay, hyper[2] = decoupled
+ * (0 / 1), hyper[3] = 0 (reserved) -- read like state[]: uniform, once per thread.  Every `_hp` entry takes the arguments
+ * of its sibling with `hyper` in place of lr and weight_decay; same grids, copy rider, mmvae_adam_set_workgroups.
+ *   decoupled == 0: the arithmetic of mmvae_adam_step, bit for bit (hyper = {lr, wd, 0, 0} against lr, wd by value).
+ *   decoupled != 0: torch.optim.AdamW -- g = clip*grad_scale*grad (clamped to +-cv under clip by value), no wd*p term;
+ *                   p *= (1 - lr*wd), in fp32 in that order; then the same moment and parameter update.
+ * Replaces torch.optim.AdamW(lr=5e-3, weight_decay=1e-6).step() (cmmvae_model.py:299-306, optim_cls="AdamW"). */
+#define MMVAE_ADAM_HYPER_FLOATS 4
+int mmvae_adam_step_hp(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const float* state,
+                       const float* hyper, float beta1, float beta2, float eps, float grad_scale, mmvae_stream_t stream);
+int mmvae_adam_step_copy_hp(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                            const float* state, const float* hyper, float beta1, float beta2, float eps, float grad_scale,
+                            int copy_n, const float* copy_src, float* copy_dst, mmvae_stream_t stream);
 
 /* Adam over a list of arena segments in ONE launch (one workgroup per job): the update of a conditional-layer model
  * touches only the parameter tensors that took part in the step -- torch.optim.Adam skips parameters whose .grad is
@@ -387,6 +405,10 @@ typedef struct {
 int mmvae_adam_step_jobs(int n_jobs, const mmvae_adam_job* jobs_dev, float* param, const float* grad, float* exp_avg,
                          float* exp_avg_sq, const float* state, float lr, float beta1, float beta2, float eps,
                          float weight_decay, float grad_scale, mmvae_stream_t stream);
+/* (ABI 13) lr / weight_decay / decay mode from `hyper` (see mmvae_adam_step_hp) */
+int mmvae_adam_step_jobs_hp(int n_jobs, const mmvae_adam_job* jobs_dev, float* param, const float* grad, float* exp_avg,
+                            float* exp_avg_sq, const float* state, const float* hyper, float beta1, float beta2, float eps,
+                            float grad_scale, mmvae_stream_t stream);
 /* partials[j] = sum of squares of job j's segment of `grad` (0 for len == 0): the norm pass of such a step, over the
  * tensors that took part only.  A captured program launches a FIXED n_jobs and pads the table with empty jobs (both
  * job kernels return at once for them); mmvae_adam_prepare then sums the n_jobs partials. */
@@ -794,6 +816,15 @@ typedef struct {
     float lr, beta1, beta2, eps, weight_decay, grad_scale;
 } mmvae_adam_arena;
 int mmvae_adam_step_multi(int n_arenas, const mmvae_adam_arena* arenas_dev, int64_t max_n, mmvae_stream_t stream);
+/* (ABI 13) each arena's lr / weight_decay / decay mode from its own `hyper` words (see mmvae_adam_step_hp) */
+typedef struct {
+    float *p, *g, *m, *v;
+    const float* state;
+    const float* hyper;
+    int64_t n;
+    float beta1, beta2, eps, grad_scale;
+} mmvae_adam_arena_hp;
+int mmvae_adam_step_multi_hp(int n_arenas, const mmvae_adam_arena_hp* arenas_dev, int64_t max_n, mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Sparse weight gradient of the first encoder layer (ABI 6).  Replaces the autograd of nn.Linear

@@ -21,6 +21,7 @@ GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 GEMM_RELU, GEMM_ACCUMULATE, GEMM_RAW_SLABS, GEMM_OPERAND_SLACK = 1, 2, 4, 8
 GEMM_PRECISION_F32, GEMM_PRECISION_BF16X3 = 0, 1
 ADAM_STATE_FLOATS = 8
+ADAM_HYPER_FLOATS = 4  # lr, weight_decay, decoupled (0 / 1), reserved: the device words of the `_hp` Adam entries
 PREPARE_NORM, PREPARE_ADVANCE = 1, 2
 
 _p = C.c_void_p
@@ -98,8 +99,11 @@ PROTOTYPES = {
     "mmvae_adam_prepare": (_i, [_l, _p, _f, _f, _f, _f, _p, _u, _p]),
     "mmvae_grad_sqnorm_ranges_prepare": (_i, [_i, _p, _p, _p, _p, _l, _p, _f, _f, _f, _f, _p, _u, _p]),
     "mmvae_adam_step": (_i, [_l, _p, _p, _p, _p, _p, _f, _f, _f, _f, _f, _f, _p]),
+    "mmvae_adam_step_hp": (_i, [_l, _p, _p, _p, _p, _p, _p, _f, _f, _f, _f, _p]),
+    "mmvae_adam_step_copy_hp": (_i, [_l, _p, _p, _p, _p, _p, _p, _f, _f, _f, _f, _i, _p, _p, _p]),
     "mmvae_adam_step_copy": (_i, [_l, _p, _p, _p, _p, _p, _f, _f, _f, _f, _f, _f, _i, _p, _p, _p]),
     "mmvae_adam_step_jobs": (_i, [_i, _p, _p, _p, _p, _p, _p, _f, _f, _f, _f, _f, _f, _p]),
+    "mmvae_adam_step_jobs_hp": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _f, _p]),
     "mmvae_grad_sqnorm_jobs": (_i, [_i, _p, _p, _p, _p]),
     "mmvae_grad_zero_flagged_jobs": (_i, [_i, _p, _p, _p]),
     "mmvae_jobs_pack": (_i, [_i, _p, _p, _p, _p]),
@@ -167,6 +171,7 @@ PROTOTYPES = {
     "mmvae_adv_dw_prepare": (_i, [_i, _p, C.POINTER(_i), C.POINTER(_i)]),
     "mmvae_adv_dw_f32": (_i, [_i, _p, _i, _i, _p, _p, _p, _i, _p, _i, _p]),
     "mmvae_adam_step_multi": (_i, [_i, _p, _l, _p]),
+    "mmvae_adam_step_multi_hp": (_i, [_i, _p, _l, _p]),
     "mmvae_ell_from_dense_f32": (_i, [_i, _i, _p, _l, _i, _p, _p, _p, _p]),
     "mmvae_dw_sparse_ell_f32": (_i, [_i, _i, _i, _p, _l, _p, _p, _p, _i, _p, _l, _p]),
 }
@@ -227,6 +232,13 @@ class AdamArena(C.Structure):
     """mmvae_adam_arena: one optimiser's arenas in a mmvae_adam_step_multi launch."""
     _fields_ = [("p", _p), ("g", _p), ("m", _p), ("v", _p), ("state", _p), ("n", _l), ("lr", _f), ("beta1", _f),
                 ("beta2", _f), ("eps", _f), ("weight_decay", _f), ("grad_scale", _f)]
+
+
+class AdamArenaHp(C.Structure):
+    """mmvae_adam_arena_hp: one optimiser's arenas in a mmvae_adam_step_multi_hp launch (lr / weight decay / decay mode
+    from the optimiser's `hyper` device words)."""
+    _fields_ = [("p", _p), ("g", _p), ("m", _p), ("v", _p), ("state", _p), ("hyper", _p), ("n", _l), ("beta1", _f),
+                ("beta2", _f), ("eps", _f), ("grad_scale", _f)]
 
 
 class HipLibraryError(RuntimeError):

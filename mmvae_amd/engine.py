@@ -240,7 +240,8 @@ class StepEngine:
             return "conditional layers with MMVAE_ENGINE_CONDITIONALS=0"
         opts = model.optimizers()
         if not all(isinstance(o, HipAdam) and o._hip for o in opts):
-            return "an optimiser that is not the HIP Adam (mmvae_amd.optim.HipAdam on device arenas)"
+            return ("an optimiser that is not the HIP Adam (mmvae_amd.optim.HipAdam on device arenas, coupled or "
+                    "decoupled weight decay)")
         if cl is not None:
             # (ranks see different conditions: the blocks that step are the UNION over the ranks, CondProgram.load)
             if not CondProgram.supported(cl, model.get_optimizers()["vae"], m.vae.encoder.mean_encoder.out_features):
@@ -398,13 +399,16 @@ class StepEngine:
                                                                             for _ in range(3)])[:3]
 
     def _signature(self) -> tuple:
-        """Everything a captured training program freezes at build time: optimiser hyper-parameters, clip values, the
+        """Everything a captured training program freezes at build time: the optimisers' betas and eps, clip values, the
         adversarial weight, world size / gradient exchange.  Compared on every training step; a change (dist.attach()
-        after the first step, a new learning rate through param_groups or HipAdam.load_state_dict, an edited
-        autograd_config) drops the plans and their graphs, which are then rebuilt with the current values."""
+        after the first step, new betas through param_groups or HipAdam.load_state_dict, an edited autograd_config)
+        drops the plans and their graphs, which are then rebuilt with the current values.  The learning rate, the
+        weight decay and the decay mode are NOT part of it: the Adam kernels read them from each optimiser's device
+        words (HipAdam.hyper_dev), which _sync_hyper() rewrites ahead of a step when param_groups has changed -- a
+        learning-rate schedule costs a captured program one small write per step, not a re-capture."""
         ac = self.model.autograd_config
         clip = lambda c: (float(c.val), c.algorithm or "norm") if (c and c.val) else (0.0, "norm")  # noqa: E731
-        per_opt = tuple((g["lr"], g["eps"], g["weight_decay"], tuple(g["betas"]), o.reducer is not None, o.grad_scale)
+        per_opt = tuple((g["eps"], tuple(g["betas"]), o.reducer is not None, o.grad_scale)
                         for o in self.model.optimizers() for g in o.param_groups[:1])
         return (per_opt, clip(ac.vae_gradient_clip), clip(ac.expert_gradient_clip), clip(ac.adversarial_gradient_clip),
                 float(self.model.adv_weight), mdist.world_size(), mdist.collectives_active())
@@ -480,15 +484,16 @@ class StepEngine:
     def _check_signature(self) -> None:
         sig = self._signature()
         if sig != self._sig:
-            # A captured program freezes the optimiser's hyper-parameters: a per-step schedule (learning-rate warm-up)
-            # rebuilds and re-captures every step -- correct, but milliseconds instead of one replay.  Say so once.
+            # A captured program freezes betas, eps, clip values and the adversarial weight: changing one of them on every
+            # step rebuilds and re-captures every step -- correct, but milliseconds instead of one replay.  Say so once.
+            # (The learning rate and the weight decay are device words: schedules over them do not come here.)
             self._sig_changes += 1
             if self._sig_changes == 3:
                 import warnings
 
-                warnings.warn("mmvae_amd.engine: optimiser settings changed on several training steps; every change drops "
-                              "the captured step programs and re-captures them (a learning-rate schedule stepping per "
-                              "batch costs milliseconds per step) -- change them per epoch, or set use_engine=False")
+                warnings.warn("mmvae_amd.engine: frozen step settings (betas, eps, clip values, adv_weight) changed on "
+                              "several training steps; every change drops the captured step programs and re-captures them "
+                              "(milliseconds per step) -- change them per epoch, or set use_engine=False")
             self._drop_train_plans()
             self._configure_parallel()
             self._sig = sig
@@ -674,6 +679,17 @@ class StepEngine:
             self.klw_dev.fill_(klw)
             self._klw_host = klw
 
+    def _sync_hyper(self, expert_id: str) -> None:
+        """Learning rate / weight decay / decay mode of every optimiser a training program of `expert_id` steps -> their
+        device words, when param_groups has changed (HipAdam.sync_hyper: fill kernels on the current stream, nothing
+        when unchanged).  Called behind the wait on the expert's pending deferred update: an update still running on the
+        communication stream reads the words of ITS step."""
+        o = self.opts
+        o["vae"].sync_hyper()
+        o["experts"][expert_id].sync_hyper()
+        for opt in (o.get("adversarials") or {}).values():
+            opt.sync_hyper()
+
     # ------------------------------------------------------------------------------------- eval / predict (f3)
     def _forward_only(self, mode: str, x: torch.Tensor, expert_id: str, metadata=None):
         """Forward-only plan (no autograd, no gradients, no optimiser): eval-mode BatchNorm (running statistics), no
@@ -845,6 +861,7 @@ class StepEngine:
         ev = self._pending.pop(expert_id, None)
         if ev is not None:  # this expert's previous (deferred) update must land before its parameters are read
             torch.cuda.current_stream().wait_event(ev)
+        self._sync_hyper(expert_id)
         self.last_plan = plan  # introspection (tests read the activations the step left in its buffers)
         ev = plan.run()
         if ev is not None:

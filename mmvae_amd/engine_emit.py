@@ -632,8 +632,8 @@ class PlanEmit:
             flags = _lib.PREPARE_NORM | (_lib.PREPARE_ADVANCE if (advance and step) else 0)
             self._emit(self.lib.mmvae_adam_prepare, c.max_jobs, _p(c.partials), max_norm, gs, b1, b2, _p(opt.state_dev), flags)
             if step:
-                self._emit(self.lib.mmvae_adam_step_jobs, c.max_jobs, c.jobs_ptr, _p(a.data), _p(a.grad), _p(a.exp_avg),
-                           _p(a.exp_avg_sq), _p(opt.state_dev), g["lr"], b1, b2, g["eps"], g["weight_decay"], gs)
+                self._emit(self.lib.mmvae_adam_step_jobs_hp, c.max_jobs, c.jobs_ptr, _p(a.data), _p(a.grad), _p(a.exp_avg),
+                           _p(a.exp_avg_sq), _p(opt.state_dev), _p(opt.hyper_dev), b1, b2, g["eps"], gs)
             return
         cover = sorted(self._sq_cover.pop(id(opt), []))
         flags = _lib.PREPARE_NORM | (_lib.PREPARE_ADVANCE if (advance and step) else 0)
@@ -664,12 +664,12 @@ class PlanEmit:
             self._emit(self.lib.mmvae_adam_prepare, npart, _p(buf), max_norm, gs, b1, b2, _p(opt.state_dev), flags)
         pr = ("adam_expert", 28.0 * a.numel) if opt is self.opt_exp else None  # bytes: p, g, m, v read; p, m, v written
         if step and tail_copy is not None:  # (n, src, dst): the step's logged scalars ride on this launch
-            self._emit(self.lib.mmvae_adam_step_copy, a.numel, _p(a.data), _p(a.grad), _p(a.exp_avg), _p(a.exp_avg_sq),
-                       _p(opt.state_dev), g["lr"], b1, b2, g["eps"], g["weight_decay"], gs, tail_copy[0],
-                       _p(tail_copy[1]), _p(tail_copy[2]), probe=pr)
+            self._emit(self.lib.mmvae_adam_step_copy_hp, a.numel, _p(a.data), _p(a.grad), _p(a.exp_avg), _p(a.exp_avg_sq),
+                       _p(opt.state_dev), _p(opt.hyper_dev), b1, b2, g["eps"], gs, tail_copy[0], _p(tail_copy[1]),
+                       _p(tail_copy[2]), probe=pr)
         elif step:
-            self._emit(self.lib.mmvae_adam_step, a.numel, _p(a.data), _p(a.grad), _p(a.exp_avg), _p(a.exp_avg_sq),
-                       _p(opt.state_dev), g["lr"], b1, b2, g["eps"], g["weight_decay"], gs, probe=pr)
+            self._emit(self.lib.mmvae_adam_step_hp, a.numel, _p(a.data), _p(a.grad), _p(a.exp_avg), _p(a.exp_avg_sq),
+                       _p(opt.state_dev), _p(opt.hyper_dev), b1, b2, g["eps"], gs, probe=pr)
         if step and pr:
             self.probe_meta["adam_expert"].update(bound="hbm", cus=0, shape=f"{a.numel} parameters, 28 B each")
 
@@ -700,9 +700,9 @@ class PlanEmit:
         flags = _lib.PREPARE_NORM | (_lib.PREPARE_ADVANCE if (advance and step) else 0)
         self._emit(lib.mmvae_adam_prepare, W, _p(allsq), max_norm, gs, b1, b2, _p(opt.state_dev), flags)
         if step and n_loc > 0:
-            self._emit(lib.mmvae_adam_step, n_loc, a.data.data_ptr() + 4 * lo, a.grad.data_ptr() + 4 * lo,
-                       a.exp_avg.data_ptr() + 4 * lo, a.exp_avg_sq.data_ptr() + 4 * lo, _p(opt.state_dev), g["lr"], b1, b2,
-                       g["eps"], g["weight_decay"], gs, probe=("adam_expert", 28.0 * n_loc))
+            self._emit(lib.mmvae_adam_step_hp, n_loc, a.data.data_ptr() + 4 * lo, a.grad.data_ptr() + 4 * lo,
+                       a.exp_avg.data_ptr() + 4 * lo, a.exp_avg_sq.data_ptr() + 4 * lo, _p(opt.state_dev),
+                       _p(opt.hyper_dev), b1, b2, g["eps"], gs, probe=("adam_expert", 28.0 * n_loc))
             self.probe_meta["adam_expert"].update(bound="hbm", cus=0, shape=f"{n_loc} parameters (1/{W} of the arena), 28 B each")
         if step:
             self._cut(("ag_params", opt))

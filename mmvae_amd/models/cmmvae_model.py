@@ -38,7 +38,10 @@ def _ce_sum(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
 
 class CMMVAEModel(BaseModel):
     def __init__(self, module: CMMVAE, adv_weight: Optional[float] = None,
-                 autograd_config: Optional[AutogradConfig] = None, *args, use_engine: bool = True, **kwargs):
+                 autograd_config: Optional[AutogradConfig] = None, *args, use_engine: bool = True,
+                 lr_schedule_fn=None, optim_cls: str = "Adam", **kwargs):
+        """lr_schedule_fn: a mmvae_amd.modules.base.LRScheduleFn, or None (constant learning rate, nothing logged);
+        optim_cls: what configure_optimizers() builds by default -- "Adam", anything else AdamW (cmmvae_model.py:299-306)."""
         super().__init__(*args, **kwargs)
         self.module = module
         self.automatic_optimization = False  # manual optimisation (cmmvae_model.py:50-52)
@@ -49,6 +52,9 @@ class CMMVAEModel(BaseModel):
         self.use_engine = use_engine
         self._engine = None
         self.optimizer_map = None
+        self.lr_schedule_fn = lr_schedule_fn
+        self.optim_cls = optim_cls
+        self._base_lrs = None  # each optimiser's learning rate as configure_optimizers() built it (flat-list order)
 
     # ------------------------------------------------------------------------------------------ adversarial phases
     # The module path states the step the way DESIGN.md section 2 and the engine's program do: sections
@@ -120,8 +126,10 @@ class CMMVAEModel(BaseModel):
         metadata["species"] = expert_id
         engine = self._get_engine(x)
         hint, self._next_hint = getattr(self, "_next_hint", None), None
+        self._apply_lr_schedule()
         if engine is not None:
-            return engine.training_step(x, metadata, expert_id, next_batch=hint)
+            engine.training_step(x, metadata, expert_id, next_batch=hint)
+            return self._advance_lr_schedule()
         self._flush_engine()  # (a step on the module path behind engine steps: their deferred updates land first)
         if getattr(self.module.vae.encoder, "elbo_mode", "analytic") != "analytic":
             raise NotImplementedError("elbo_mode='iwae' (the opt-in full-IWAE objective) runs in the captured engine only")
@@ -157,6 +165,26 @@ class CMMVAEModel(BaseModel):
             optimizer.step()
         self.kl_annealing_fn.step()
         self.auto_log(terms, tags=[self.stage_name, expert_id])
+        self._advance_lr_schedule()
+
+    def _apply_lr_schedule(self) -> None:
+        """With a schedule: every optimiser's lr = its base lr x factor(t) ahead of training step t (t = the schedule's
+        `step_count`: the training steps this model has taken, on either path), logged as lr/{stage}.  The write goes to
+        param_groups, like a torch.optim.lr_scheduler's; HipAdam carries it to the device word its kernels read."""
+        fn = self.lr_schedule_fn
+        if fn is None:
+            return
+        optimizers = self.optimizers()
+        if self._base_lrs is None or len(self._base_lrs) != len(optimizers):  # (optimisers built by a trainer, not by us)
+            self._base_lrs = [o.param_groups[0]["lr"] for o in optimizers]
+        factor = float(fn.factor(fn.step_count))
+        for optimizer, base_lr in zip(optimizers, self._base_lrs):
+            optimizer.param_groups[0]["lr"] = base_lr * factor
+        self.log(f"lr/{self.stage_name}", self._base_lrs[0] * factor)
+
+    def _advance_lr_schedule(self) -> None:
+        if self.lr_schedule_fn is not None:
+            self.lr_schedule_fn.step()
 
     @staticmethod
     def _posterior_stats(qz):
@@ -255,13 +283,15 @@ class CMMVAEModel(BaseModel):
                 optimizer.zero_grad()
         return _map_leaves(self.optimizer_map, lambda index: flat[index])
 
-    def configure_optimizers(self, optim_cls="Adam"):
+    def configure_optimizers(self, optim_cls=None):
         """One Adam(lr=5e-3, weight_decay=1e-6) per expert, one for the VAE, one per adversary, as a flat list plus
-        `optimizer_map` (:299-351).  "Adam" builds the fused flat-arena HipAdam; torch.optim.AdamW for "AdamW"."""
+        `optimizer_map` (:299-351).  `optim_cls` (default: the constructor's): "Adam" builds the fused flat-arena HipAdam;
+        as in the reference (:299-306) anything else means AdamW -- the same HipAdam, arenas and packs with decoupled
+        weight decay, so the model stays on the captured step engine."""
+        optim_cls = self.optim_cls if optim_cls is None else optim_cls
+
         def make(params, pack=None):
-            if optim_cls == "Adam":
-                return HipAdam(params, lr=5e-3, weight_decay=1e-6, pack=pack)
-            return torch.optim.AdamW(params, lr=5e-3, weight_decay=1e-6)
+            return HipAdam(params, lr=5e-3, weight_decay=1e-6, pack=pack, decoupled_weight_decay=optim_cls != "Adam")
 
         def head_packs(adv):
             """Single-Linear heads: their weights back to back, then their biases (one GEMM over all heads)."""
@@ -280,15 +310,16 @@ class CMMVAEModel(BaseModel):
 
         optim_dict = {"experts": {eid: make(m.parameters()) for eid, m in self.module.experts.items()},
                       "vae": make(self.module.vae.parameters())}
-        if getattr(self.module.vae, "conditionals", None) is not None and optim_cls == "Adam":
+        if getattr(self.module.vae, "conditionals", None) is not None:
             # condition blocks absent from a rank's batch have no gradient there: under data parallelism the set of
             # parameters that step is the union over the ranks (HipAdam._allreduce)
             optim_dict["vae"].sparse_presence = True
         if len(self.module.adversarials) > 0:
-            optim_dict["adversarials"] = {i: make(m.parameters(), head_packs(m) if optim_cls == "Adam" else None)
+            optim_dict["adversarials"] = {i: make(m.parameters(), head_packs(m))
                                           for i, m in enumerate(self.module.adversarials, start=1)}
         optimizers: list = []
         self.optimizer_map = convert_to_flat_list_and_map(optim_dict, optimizers)
+        self._base_lrs = [o.param_groups[0]["lr"] for o in optimizers]
         return optimizers
 
     # ------------------------------------------------------------------------------------------------------ engine

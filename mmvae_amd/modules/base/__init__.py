@@ -2,6 +2,8 @@
 from .annealing_fn import KLAnnealingFn, LinearKLAnnealingFn
 from .components import (Adversarial, ConcatBlockConfig, ConditionalLayer, ConditionalLayers, Encoder, Expert, Experts,
                          FCBlock, FCBlockConfig, GradientReversalFunction)
+from .lr_schedule import LRScheduleFn, StepDecayLRFn, WarmupCosineLRFn
 
 __all__ = ["Adversarial", "ConcatBlockConfig", "ConditionalLayer", "ConditionalLayers", "Encoder", "Expert", "Experts",
-           "FCBlock", "FCBlockConfig", "GradientReversalFunction", "KLAnnealingFn", "LinearKLAnnealingFn"]
+           "FCBlock", "FCBlockConfig", "GradientReversalFunction", "KLAnnealingFn", "LinearKLAnnealingFn", "LRScheduleFn",
+           "StepDecayLRFn", "WarmupCosineLRFn"]

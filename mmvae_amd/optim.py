@@ -132,10 +132,17 @@ def arena_of(p: torch.nn.Parameter):
 
 class HipAdam(torch.optim.Optimizer):
     """Adam (coupled L2 weight decay, amsgrad=False; identical update rule to torch.optim.Adam) over a ParamArena,
-    with the gradient-norm clip fused in.  State (`step`, last pre-clip grad norm, clip coefficient) stays on device."""
+    with the gradient-norm clip fused in.  State (`step`, last pre-clip grad norm, clip coefficient) stays on device.
+    `decoupled_weight_decay=True`: torch.optim.AdamW's rule instead (p *= 1 - lr * wd ahead of the update, no wd * p
+    in the gradient); an attribute of the optimiser, not a param_groups key (checkpoints keep torch's keys).
+
+    The learning rate, the weight decay and the decay mode reach the kernels through `hyper_dev` (4 device words, the
+    `_hp` entry points of include/mmvae_hip.h), rewritten by sync_hyper() when `param_groups[0]` has changed: a
+    schedule -- the model's lr_schedule_fn, a torch.optim.lr_scheduler -- costs a captured program one small write."""
 
     def __init__(self, params, lr: float = 5e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-6,
-                 max_grad_norm: Optional[float] = None, pack: Optional[list] = None):
+                 max_grad_norm: Optional[float] = None, pack: Optional[list] = None,
+                 decoupled_weight_decay: bool = False):
         params = list(params)
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
@@ -161,6 +168,11 @@ class HipAdam(torch.optim.Optimizer):
             raise RuntimeError("HipAdam needs device parameters (or caller-enabled backend.cpu_plumbing())")
         dev = self.arena.device
         self.state_dev = torch.zeros(8, dtype=torch.float32, device=dev)  # step, norm, clip, bc1, bc2
+        # lr, weight_decay, decoupled (0 / 1), reserved.  Allocated once: captured programs hold its address.
+        self.decoupled_weight_decay = bool(decoupled_weight_decay)
+        self.hyper_dev = torch.zeros(4, dtype=torch.float32, device=dev)
+        self._hyper_host: List[Optional[float]] = [None, None, None]
+        self.sync_hyper()
         # torch.optim.Adam counts steps per parameter and skips parameters without a gradient (conditional layers:
         # the conditions absent from a batch).  While every parameter has taken part in every step the counts are all
         # equal to state_dev[0] and live on the device only; the first partial step materialises them here.
@@ -169,6 +181,21 @@ class HipAdam(torch.optim.Optimizer):
         self._inactive: List[int] = []
         if self._hip:
             self.partials = torch.empty(max(ops.sqnorm_partials(self.arena.numel), 1), dtype=torch.float32, device=dev)
+
+    def sync_hyper(self) -> bool:
+        """param_groups[0]["lr"], ["weight_decay"] and the decay mode -> `hyper_dev`, the words that differ from what the
+        device holds only.  Each is written by a fill kernel on the current stream, in stream order with the updates
+        that read it -- never a host-to-device copy (a hipMemcpyAsync behind a captured program makes the host wait for
+        that program on this runtime: DESIGN.md section 10 (iii)).  Returns whether anything was written."""
+        g = self.param_groups[0]
+        want = [float(g["lr"]), float(g["weight_decay"]), 1.0 if self.decoupled_weight_decay else 0.0]
+        wrote = False
+        for i, (new, old) in enumerate(zip(want, self._hyper_host)):
+            if new != old:
+                self.hyper_dev[i:i + 1].fill_(new)
+                self._hyper_host[i] = new
+                wrote = True
+        return wrote
 
     def sync_sharded_state(self) -> None:
         """All-gather the Adam moments after sharded steps.  COLLECTIVE: every rank of the reducer's group must call it at
@@ -298,9 +325,10 @@ class HipAdam(torch.optim.Optimizer):
         if self._inactive or self._steps is not None:
             self._step_partial(g, b1, b2, reuse)
         elif self._hip:
-            ops.clip_adam_step(a.data, a.grad, a.exp_avg, a.exp_avg_sq, self.state_dev, self.partials, lr=g["lr"],
-                               beta1=b1, beta2=b2, eps=g["eps"], weight_decay=g["weight_decay"],
-                               max_norm=self.max_grad_norm or 0.0, grad_scale=self.grad_scale, do_norm=not reuse)
+            self.sync_hyper()
+            ops.clip_adam_step(a.data, a.grad, a.exp_avg, a.exp_avg_sq, self.state_dev, self.partials, beta1=b1,
+                               beta2=b2, eps=g["eps"], max_norm=self.max_grad_norm or 0.0, grad_scale=self.grad_scale,
+                               do_norm=not reuse, hyper=self.hyper_dev)
         else:
             self._step_cpu_plumbing(g, b1, b2)
         self._norm_valid = False
@@ -380,11 +408,12 @@ class HipAdam(torch.optim.Optimizer):
             jobs = self.job_table(active, b1, b2)
             jobs_dev = torch.from_numpy(jobs.view(np.uint8)).to(a.device, non_blocking=False)
             lib = _lib.load()
-            rc = lib.mmvae_adam_step_jobs(len(jobs), jobs_dev.data_ptr(), a.data.data_ptr(), a.grad.data_ptr(),
-                                          a.exp_avg.data_ptr(), a.exp_avg_sq.data_ptr(), self.state_dev.data_ptr(),
-                                          g["lr"], b1, b2, g["eps"], g["weight_decay"], float(self.grad_scale),
-                                          torch.cuda.current_stream().cuda_stream)
-            _lib.check(rc, "mmvae_adam_step_jobs")
+            self.sync_hyper()
+            rc = lib.mmvae_adam_step_jobs_hp(len(jobs), jobs_dev.data_ptr(), a.data.data_ptr(), a.grad.data_ptr(),
+                                             a.exp_avg.data_ptr(), a.exp_avg_sq.data_ptr(), self.state_dev.data_ptr(),
+                                             self.hyper_dev.data_ptr(), b1, b2, g["eps"], float(self.grad_scale),
+                                             torch.cuda.current_stream().cuda_stream)
+            _lib.check(rc, "mmvae_adam_step_jobs_hp")
             self._keep_jobs = jobs_dev  # outlives the launch
         else:
             for j, i in enumerate(active):
@@ -393,7 +422,10 @@ class HipAdam(torch.optim.Optimizer):
                 gr = a.grad[sl] * self.grad_scale * float(clip)
                 if getattr(self, "clip_value", None):  # gradient_clip_algorithm "value" (config.py:8)
                     gr = gr.clamp(-self.clip_value, self.clip_value)
-                gr = gr + g["weight_decay"] * a.data[sl]
+                if self.decoupled_weight_decay:  # torch.optim.AdamW: the parameter decays, the gradient carries no wd * p
+                    a.data[sl].mul_(1 - g["lr"] * g["weight_decay"])
+                else:
+                    gr = gr + g["weight_decay"] * a.data[sl]
                 a.exp_avg[sl].lerp_(gr, 1 - b1)
                 a.exp_avg_sq[sl].mul_(b2).addcmul_(gr, gr, value=1 - b2)
                 denom = a.exp_avg_sq[sl].sqrt() / (float(bc2[j]) ** 0.5) + g["eps"]
@@ -416,7 +448,10 @@ class HipAdam(torch.optim.Optimizer):
         grad = grad * clip
         if getattr(self, "clip_value", None):
             grad = grad.clamp(-self.clip_value, self.clip_value)
-        grad = grad + g["weight_decay"] * a.data
+        if self.decoupled_weight_decay:  # torch.optim.AdamW: the parameter decays, the gradient carries no wd * p
+            a.data.mul_(1 - g["lr"] * g["weight_decay"])
+        else:
+            grad = grad + g["weight_decay"] * a.data
         a.exp_avg.lerp_(grad, 1 - b1)
         a.exp_avg_sq.mul_(b2).addcmul_(grad, grad, value=1 - b2)
         bc1, bc2 = 1 - b1 ** t, 1 - b2 ** t
