@@ -39,8 +39,11 @@ typedef void* mmvae_stream_t; /* hipStream_t */
 
 /* ABI version: bumped whenever an entry point is added or a signature changes (mmvae_abi_version() returns the
  * value the library was built with; bindings compare it with the header they were written against).
- *   1  round-1 surface (first 20 entry points)      2  end of round 1 (50 entry points)      3+  round 2 */
-#define MMVAE_ABI_VERSION 13
+ *   1  round-1 surface (first 20 entry points)      2  end of round 1 (50 entry points)      3+  round 2
+ *   14 removed the Adam passes that took lr and weight decay by value -- mmvae_adam_step, mmvae_adam_step_copy,
+ *      mmvae_adam_step_jobs, mmvae_adam_step_multi -- and the struct mmvae_adam_arena: their `_hp` forms of ABI 13 are the
+ *      only Adam passes.  The names are not reused, so a caller of a retired symbol fails when it loads or binds. */
+#define MMVAE_ABI_VERSION 14
 int mmvae_abi_version(void);
 const char* mmvae_build_arch(void);
 
@@ -333,14 +336,13 @@ int mmvae_sum_rows_f32(int H, int64_t n, const float* v, int64_t ld, float* out_
  *                      Always: state[2] = clip coefficient min(1, max_norm/(norm+1e-6)) (1 if max_norm <= 0),
  *                      state[3] = 1 - beta1^step, state[4] = 1 - beta2^step.
  *                      grad_scale multiplies the gradients first (DDP averaging: 1/world_size).
- * mmvae_adam_step:     g = clip*grad_scale*grad + wd*p ; m += (1-b1)(g-m) ; v = b2 v + (1-b2) g^2 ;
+ * mmvae_adam_step_hp:  g = clip*grad_scale*grad + wd*p ; m += (1-b1)(g-m) ; v = b2 v + (1-b2) g^2 ;
  *                      p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)            (torch.optim.Adam, amsgrad=False)
  *                      state[5] = cv > 0 (written by the caller; mmvae_adam_prepare never touches it): clip BY VALUE --
  *                      GradientClipConfig(algorithm="value"), config.py:8, Lightning clip_gradients ->
  *                      clip_grad_value_ -- g = clamp(clip*grad_scale*grad, -cv, cv) + wd*p (pass max_norm = 0: clip = 1).
- * mmvae_adam_step_hp (and the other `_hp` entries below): the same passes with lr, weight decay and the decay mode read
- *                      from device words (`hyper`) -- what a captured program launches, so that a learning-rate
- *                      schedule is one small write per step; decoupled mode = torch.optim.AdamW.
+ *                      lr, wd and the decay mode are read from device words (`hyper`, below), so that a learning-rate
+ *                      schedule is one small write per step of a captured program; decoupled mode = torch.optim.AdamW.
  * ------------------------------------------------------------------------------------------------------------ */
 #define MMVAE_ADAM_STATE_FLOATS 8
 #define MMVAE_PREPARE_NORM 1u
@@ -349,18 +351,13 @@ int64_t mmvae_sqnorm_partials(int64_t n);
 int mmvae_grad_sqnorm(int64_t n, const float* grad, float* partials, mmvae_stream_t stream);
 int mmvae_adam_prepare(int64_t n_partials, const float* partials, float max_norm, float grad_scale, float beta1,
                        float beta2, float* state, unsigned flags, mmvae_stream_t stream);
-/* Host-side launch state (like mmvae_gemm_set_workgroup_cap): workgroups > 0 confines mmvae_adam_step /
- * mmvae_adam_step_copy (and their _hp siblings) to that many compute units (1024-thread workgroups, one per CU) for callers that run the update
- * beside a kernel of another stream whose grid is capped to the remaining units; 0 = the chip-filling grid.
+/* Host-side launch state (like mmvae_gemm_set_workgroup_cap): workgroups > 0 confines mmvae_adam_step_hp /
+ * mmvae_adam_step_copy_hp to that many compute units (1024-thread workgroups, one per CU) for callers that run the
+ * update beside a kernel of another stream whose grid is capped to the remaining units; 0 = the chip-filling grid.
  * Elementwise work: results do not depend on it.  Replaces nothing in the reference (torch.optim.Adam.step,
  * cmmvae_model.py:203-213, is stream-ordered behind backward). */
 int mmvae_adam_set_workgroups(int workgroups);
 int mmvae_adam_get_workgroups(void);
-/* mmvae_adam_step with a rider: workgroup 0 also copies copy_n floats copy_src -> copy_dst (both must not overlap the
- * arenas) -- the step's logged scalars into a log buffer without a launch of their own.  copy_n = 0: mmvae_adam_step. */
-int mmvae_adam_step_copy(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
-                         const float* state, float lr, float beta1, float beta2, float eps, float weight_decay,
-                         float grad_scale, int copy_n, const float* copy_src, float* copy_dst, mmvae_stream_t stream);
 /* The norm pass over 1..4 ranges of a gradient arena (e.g. what no fused GEMM epilogue covers) AND mmvae_adam_prepare
  * in one launch: range i = grads[i][0 .. lens[i]); its mmvae_sqnorm_partials(lens[i]) partials are written behind each
  * other at `partials`; the workgroup that finishes last (`ticket`: one zero-initialised word the kernel resets) sums the
@@ -370,21 +367,19 @@ int mmvae_grad_sqnorm_ranges_prepare(int n_ranges, const float* const* grads, co
                                      unsigned* ticket, int64_t n_partials_all, const float* partials_all, float max_norm,
                                      float grad_scale, float beta1, float beta2, float* state, unsigned flags,
                                      mmvae_stream_t stream);
-int mmvae_adam_step(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const float* state,
-                    float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
-                    mmvae_stream_t stream);
-/* (ABI 13) The same passes with the learning rate, the weight decay and the decay mode read from DEVICE memory, so that
+/* The Adam passes (`_hp`, ABI 13) read the learning rate, the weight decay and the decay mode from DEVICE memory, so that
  * a captured program follows a learning-rate schedule (one small write per step) instead of holding them as constants.
  * `hyper`: MMVAE_ADAM_HYPER_FLOATS floats per optimiser -- hyper[0] = lr, hyper[1] = weight_decay, hyper[2] = decoupled
- * (0 / 1), hyper[3] = 0 (reserved) -- read like state[]: uniform, once per thread.  Every `_hp` entry takes the arguments
- * of its sibling with `hyper` in place of lr and weight_decay; same grids, copy rider, mmvae_adam_set_workgroups.
- *   decoupled == 0: the arithmetic of mmvae_adam_step, bit for bit (hyper = {lr, wd, 0, 0} against lr, wd by value).
+ * (0 / 1), hyper[3] = 0 (reserved) -- read like state[]: uniform, once per thread.
+ *   decoupled == 0: the update rule above (torch.optim.Adam; a caller with a constant lr fills the four words once).
  *   decoupled != 0: torch.optim.AdamW -- g = clip*grad_scale*grad (clamped to +-cv under clip by value), no wd*p term;
  *                   p *= (1 - lr*wd), in fp32 in that order; then the same moment and parameter update.
  * Replaces torch.optim.AdamW(lr=5e-3, weight_decay=1e-6).step() (cmmvae_model.py:299-306, optim_cls="AdamW"). */
 #define MMVAE_ADAM_HYPER_FLOATS 4
 int mmvae_adam_step_hp(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const float* state,
                        const float* hyper, float beta1, float beta2, float eps, float grad_scale, mmvae_stream_t stream);
+/* mmvae_adam_step_hp with a rider: workgroup 0 also copies copy_n floats copy_src -> copy_dst (both must not overlap the
+ * arenas) -- the step's logged scalars into a log buffer without a launch of their own.  copy_n = 0: mmvae_adam_step_hp. */
 int mmvae_adam_step_copy_hp(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                             const float* state, const float* hyper, float beta1, float beta2, float eps, float grad_scale,
                             int copy_n, const float* copy_src, float* copy_dst, mmvae_stream_t stream);
@@ -402,10 +397,7 @@ typedef struct {
     float bc1, bc2;
     int32_t reserved;
 } mmvae_adam_job;
-int mmvae_adam_step_jobs(int n_jobs, const mmvae_adam_job* jobs_dev, float* param, const float* grad, float* exp_avg,
-                         float* exp_avg_sq, const float* state, float lr, float beta1, float beta2, float eps,
-                         float weight_decay, float grad_scale, mmvae_stream_t stream);
-/* (ABI 13) lr / weight_decay / decay mode from `hyper` (see mmvae_adam_step_hp) */
+/* lr / weight_decay / decay mode from `hyper` (see mmvae_adam_step_hp) */
 int mmvae_adam_step_jobs_hp(int n_jobs, const mmvae_adam_job* jobs_dev, float* param, const float* grad, float* exp_avg,
                             float* exp_avg_sq, const float* state, const float* hyper, float beta1, float beta2, float eps,
                             float grad_scale, mmvae_stream_t stream);
@@ -417,7 +409,7 @@ int mmvae_grad_sqnorm_jobs(int n_jobs, const mmvae_adam_job* jobs_dev, const flo
 /* grad[job.offset .. +job.len) = 0 for every job whose `reserved & 3` is 1 or 2 (the others return at once).  1: a
  * segment that takes part in this step only because another rank produced a gradient for it -- this rank contributes
  * zeros to the all-reduce that follows.  2: a "retired" segment (stepped last time, not now): zeroed so that a dense
- * all-reduce never sums stale values; mmvae_grad_sqnorm_jobs / mmvae_adam_step_jobs skip such jobs. */
+ * all-reduce never sums stale values; mmvae_grad_sqnorm_jobs / mmvae_adam_step_jobs_hp skip such jobs. */
 int mmvae_grad_zero_flagged_jobs(int n_jobs, const mmvae_adam_job* jobs_dev, float* grad, mmvae_stream_t stream);
 /* Gather the first n_jobs segments of a job table into a staging buffer and scatter them back: a gradient exchange over
  * the tensors that took part moves the staging buffer instead of the whole arena (conditional layers: hundreds of
@@ -732,7 +724,7 @@ int mmvae_cond_linear_bwd_dw_multi(int n_pos, int n_chunks, const int32_t* chunk
  *       launch.  The jobs of an optimiser must cover its whole gradient arena for that norm to be the arena's.  With
  *       `adv_jobs_dev` its first workgroup also sums the per-cell losses of every adversary (fp64, fixed order) into
  *       loss_each[h] / loss_total and stores the sum of total_scale * loss_total over the adversaries in *total_loss.
- *   mmvae_adam_step_multi   mmvae_adam_step over several optimisers' arenas in one launch.
+ *   mmvae_adam_step_multi_hp   mmvae_adam_step_hp over several optimisers' arenas in one launch.
  * Limits: <= 4 encoder layers, <= 8 heads, widths <= 1024 (LDS permitting: mmvae_adv_pass_plan), any B.
  * ------------------------------------------------------------------------------------------------------------ */
 #define MMVAE_ADV_MAX_LAYERS 4
@@ -809,14 +801,7 @@ int mmvae_adv_dw_f32(int n_jobs, const mmvae_adv_dw_job* jobs_dev, int total_blo
                      const mmvae_adv_opt* opts_dev, float* partials, uint32_t* ticket, int n_adv,
                      const mmvae_adv_job* adv_jobs_dev, int fast, mmvae_stream_t stream);
 
-typedef struct {
-    float *p, *g, *m, *v;
-    const float* state;
-    int64_t n;
-    float lr, beta1, beta2, eps, weight_decay, grad_scale;
-} mmvae_adam_arena;
-int mmvae_adam_step_multi(int n_arenas, const mmvae_adam_arena* arenas_dev, int64_t max_n, mmvae_stream_t stream);
-/* (ABI 13) each arena's lr / weight_decay / decay mode from its own `hyper` words (see mmvae_adam_step_hp) */
+/* each arena's lr / weight_decay / decay mode from its own `hyper` words (see mmvae_adam_step_hp) */
 typedef struct {
     float *p, *g, *m, *v;
     const float* state;

@@ -98,11 +98,8 @@ PROTOTYPES = {
     "mmvae_grad_sqnorm": (_i, [_l, _p, _p, _p]),
     "mmvae_adam_prepare": (_i, [_l, _p, _f, _f, _f, _f, _p, _u, _p]),
     "mmvae_grad_sqnorm_ranges_prepare": (_i, [_i, _p, _p, _p, _p, _l, _p, _f, _f, _f, _f, _p, _u, _p]),
-    "mmvae_adam_step": (_i, [_l, _p, _p, _p, _p, _p, _f, _f, _f, _f, _f, _f, _p]),
     "mmvae_adam_step_hp": (_i, [_l, _p, _p, _p, _p, _p, _p, _f, _f, _f, _f, _p]),
     "mmvae_adam_step_copy_hp": (_i, [_l, _p, _p, _p, _p, _p, _p, _f, _f, _f, _f, _i, _p, _p, _p]),
-    "mmvae_adam_step_copy": (_i, [_l, _p, _p, _p, _p, _p, _f, _f, _f, _f, _f, _f, _i, _p, _p, _p]),
-    "mmvae_adam_step_jobs": (_i, [_i, _p, _p, _p, _p, _p, _p, _f, _f, _f, _f, _f, _f, _p]),
     "mmvae_adam_step_jobs_hp": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _f, _p]),
     "mmvae_grad_sqnorm_jobs": (_i, [_i, _p, _p, _p, _p]),
     "mmvae_grad_zero_flagged_jobs": (_i, [_i, _p, _p, _p]),
@@ -170,7 +167,6 @@ PROTOTYPES = {
     "mmvae_adv_pass_f32": (_i, [_i, _p, _i, _i, _i, _i, _z, _p]),
     "mmvae_adv_dw_prepare": (_i, [_i, _p, C.POINTER(_i), C.POINTER(_i)]),
     "mmvae_adv_dw_f32": (_i, [_i, _p, _i, _i, _p, _p, _p, _i, _p, _i, _p]),
-    "mmvae_adam_step_multi": (_i, [_i, _p, _l, _p]),
     "mmvae_adam_step_multi_hp": (_i, [_i, _p, _l, _p]),
     "mmvae_ell_from_dense_f32": (_i, [_i, _i, _p, _l, _i, _p, _p, _p, _p]),
     "mmvae_dw_sparse_ell_f32": (_i, [_i, _i, _i, _p, _l, _p, _p, _p, _i, _p, _l, _p]),
@@ -226,12 +222,6 @@ class AdvOpt(C.Structure):
     """mmvae_adv_opt: one optimiser of a mmvae_adv_dw_f32 launch (norm / clip / step bookkeeping)."""
     _fields_ = [("state", _p), ("norm_out", _p), ("max_norm", _f), ("grad_scale", _f), ("beta1", _f), ("beta2", _f),
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
-
-
-class AdamArena(C.Structure):
-    """mmvae_adam_arena: one optimiser's arenas in a mmvae_adam_step_multi launch."""
-    _fields_ = [("p", _p), ("g", _p), ("m", _p), ("v", _p), ("state", _p), ("n", _l), ("lr", _f), ("beta1", _f),
-                ("beta2", _f), ("eps", _f), ("weight_decay", _f), ("grad_scale", _f)]
 
 
 class AdamArenaHp(C.Structure):

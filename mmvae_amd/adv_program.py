@@ -53,7 +53,7 @@ class AdvNet:
     gbh: Optional[torch.Tensor]
     col: List[int]
     classes: List[int]
-    opt: object = None       # HipAdam (arena, state_dev, param_groups) or None
+    opt: object = None       # HipAdam (arena, state_dev, hyper_dev, param_groups) or None
 
 
 def supported(lib, net: AdvNet, B: int, splits: int = 1, tiles: int = 0):
@@ -204,25 +204,19 @@ class AdvProgram:
             self.dw_partials = torch.zeros(total.value, dtype=torch.float32, device=self.device)
 
     def build_adam(self, grad_scale: float = 1.0) -> None:
-        """The arena table of the adversaries' Adam launch.  Optimisers that carry device words for lr / weight decay /
-        decay mode (HipAdam.hyper_dev, kept current by HipAdam.sync_hyper) get the `_hp` launch, which reads them there;
-        an optimiser-like object without them (arenas, state words and one param group are all AdvProgram asks for)
-        gets the by-value launch with its param group's lr and weight decay as they are now."""
-        self.adam_hp = all(getattr(n.opt, "hyper_dev", None) is not None for n in self.nets)
-        rec = _lib.AdamArenaHp if self.adam_hp else _lib.AdamArena
+        """The arena table of the adversaries' Adam launch.  The launch reads lr / weight decay / decay mode from each
+        optimiser's device words (HipAdam.hyper_dev, kept current by HipAdam.sync_hyper): an optimiser-like object must
+        carry `hyper_dev` beside its arenas, state words and one param group."""
         arr = []
         for n in self.nets:
             a, g = n.opt.arena, n.opt.param_groups[0]
-            e = rec()
+            e = _lib.AdamArenaHp()
             e.p, e.g, e.m, e.v, e.state, e.n = _p(a.data), _p(a.grad), _p(a.exp_avg), _p(a.exp_avg_sq), _p(n.opt.state_dev), a.numel
-            if self.adam_hp:
-                e.hyper = _p(n.opt.hyper_dev)
-            else:
-                e.lr, e.weight_decay = g["lr"], g["weight_decay"]
+            e.hyper = _p(n.opt.hyper_dev)
             (e.beta1, e.beta2), e.eps = g["betas"], g["eps"]
             e.grad_scale = float(grad_scale)
             arr.append(e)
-        self.adam_table = self._to_device((rec * len(arr))(*arr))
+        self.adam_table = self._to_device((_lib.AdamArenaHp * len(arr))(*arr))
         self.adam_max_n = max(n.opt.arena.numel for n in self.nets)
 
     # ------------------------------------------------------------------------------------------------ launches
@@ -238,5 +232,5 @@ class AdvProgram:
                                              t["jobs"].data_ptr(), t["dw_fast"], _stream()), "mmvae_adv_dw_f32")
 
     def launch_adam(self) -> None:
-        name = "mmvae_adam_step_multi_hp" if self.adam_hp else "mmvae_adam_step_multi"
-        _lib.check(getattr(self.lib, name)(len(self.nets), self.adam_table.data_ptr(), self.adam_max_n, _stream()), name)
+        _lib.check(self.lib.mmvae_adam_step_multi_hp(len(self.nets), self.adam_table.data_ptr(), self.adam_max_n, _stream()),
+                   "mmvae_adam_step_multi_hp")

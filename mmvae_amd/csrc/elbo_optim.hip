@@ -568,8 +568,8 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
     p = p - step_size * (m / denom);
 }
 
-// The `_hp` entry points read the learning rate, the weight decay and the decay mode from a device array (`hyper`,
-// MMVAE_ADAM_HYPER_FLOATS words: lr, weight_decay, decoupled, reserved) instead of taking them by value: a captured
+// The Adam entry points read the learning rate, the weight decay and the decay mode from a device array (`hyper`,
+// MMVAE_ADAM_HYPER_FLOATS words: lr, weight_decay, decoupled, reserved), never as launch arguments: a captured
 // program then follows a learning-rate schedule through one small write per step.  Uniform, read once per thread
 // outside the element loop, like state[].  decoupled != 0 is torch.optim.AdamW's rule: the gradient carries no wd * p
 // term (wd = 0 below: the product adds an exact zero), the parameter is multiplied by 1 - lr * wd ahead of the moment and
@@ -578,38 +578,33 @@ __device__ __forceinline__ float mul_uncontracted(float a, float b) {
 #pragma clang fp contract(off)
     return a * b;
 }
-template <bool HP>
 __device__ __forceinline__ void adam_hyper(const float* __restrict__ hyper, float& lr, float& wd, float& decay) {
     decay = 1.f;
-    if constexpr (HP) {
-        lr = hyper[0];
-        wd = hyper[1];
-        if (hyper[2] != 0.f) {
-            decay = 1.f - mul_uncontracted(lr, wd);
-            wd = 0.f;
-        }
+    lr = hyper[0];
+    wd = hyper[1];
+    if (hyper[2] != 0.f) {
+        decay = 1.f - mul_uncontracted(lr, wd);
+        wd = 0.f;
     }
 }
-// One element: with decay = 1 and the caller's wd (HP, coupled) exactly adam_one.
-template <bool HP>
+// One element: with decay = 1 and the caller's wd (coupled) exactly adam_one.
 __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float gmul, float wd, float decay,
                                           float b1, float b2, float step_size, float inv_bc2_sqrt, float eps, float cv) {
-    if constexpr (HP) p = mul_uncontracted(p, decay);
+    p = mul_uncontracted(p, decay);
     adam_one(p, g, m, v, gmul, wd, b1, b2, step_size, inv_bc2_sqrt, eps, cv);
 }
 
-template <bool HP>
 __device__ __forceinline__ void adam_step_body(int64_t n, float* __restrict__ p, const float* __restrict__ g,
                                                float* __restrict__ m, float* __restrict__ v,
                                                const float* __restrict__ state, const float* __restrict__ hyper,
-                                               float lr, float b1, float b2, float eps, float wd, float grad_scale,
-                                               int vec, int copy_n, const float* copy_src, float* copy_dst) {
+                                               float b1, float b2, float eps, float grad_scale, int vec, int copy_n,
+                                               const float* copy_src, float* copy_dst) {
     // optional rider: a small device-to-device copy (the step's logged scalars into the plan's log buffer) done by
     // workgroup 0 -- instead of a launch of its own behind the longest kernel of the step
     if (copy_n > 0 && blockIdx.x == 0)
         for (int i = threadIdx.x; i < copy_n; i += blockDim.x) copy_dst[i] = copy_src[i];
-    float decay;
-    adam_hyper<HP>(hyper, lr, wd, decay);
+    float lr, wd, decay;
+    adam_hyper(hyper, lr, wd, decay);
     const float gmul = state[2] * grad_scale;
     const float step_size = lr / state[3];
     const float inv_bc2_sqrt = 1.f / sqrtf(state[4]);
@@ -635,7 +630,7 @@ __device__ __forceinline__ void adam_step_body(int64_t n, float* __restrict__ p,
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float pe = pp[e], me = mm[e], ve = vw[e];
-                adam_elem<HP>(pe, gg[e], me, ve, gmul, wd, decay, b1, b2, step_size, inv_bc2_sqrt, eps, cv);
+                adam_elem(pe, gg[e], me, ve, gmul, wd, decay, b1, b2, step_size, inv_bc2_sqrt, eps, cv);
                 pp[e] = pe;
                 mm[e] = me;
                 vw[e] = ve;
@@ -654,27 +649,20 @@ __device__ __forceinline__ void adam_step_body(int64_t n, float* __restrict__ p,
 #endif
         }
         for (int64_t i = nv * 4 + tid0; i < n; i += stride)
-            adam_elem<HP>(p[i], g[i], m[i], v[i], gmul, wd, decay, b1, b2, step_size, inv_bc2_sqrt, eps, cv);
+            adam_elem(p[i], g[i], m[i], v[i], gmul, wd, decay, b1, b2, step_size, inv_bc2_sqrt, eps, cv);
     } else {
         for (int64_t i = tid0; i < n; i += stride)
-            adam_elem<HP>(p[i], g[i], m[i], v[i], gmul, wd, decay, b1, b2, step_size, inv_bc2_sqrt, eps, cv);
+            adam_elem(p[i], g[i], m[i], v[i], gmul, wd, decay, b1, b2, step_size, inv_bc2_sqrt, eps, cv);
     }
 }
 
-__global__ __launch_bounds__(256) void adam_step_kernel(int64_t n, float* __restrict__ p, const float* __restrict__ g,
-                                                        float* __restrict__ m, float* __restrict__ v,
-                                                        const float* __restrict__ state, float lr, float b1, float b2,
-                                                        float eps, float wd, float grad_scale, int vec, int copy_n,
-                                                        const float* copy_src, float* copy_dst) {
-    adam_step_body<false>(n, p, g, m, v, state, nullptr, lr, b1, b2, eps, wd, grad_scale, vec, copy_n, copy_src, copy_dst);
-}
 __global__ __launch_bounds__(256) void adam_step_hp_kernel(int64_t n, float* __restrict__ p, const float* __restrict__ g,
                                                            float* __restrict__ m, float* __restrict__ v,
                                                            const float* __restrict__ state,
                                                            const float* __restrict__ hyper, float b1, float b2, float eps,
                                                            float grad_scale, int vec, int copy_n, const float* copy_src,
                                                            float* copy_dst) {
-    adam_step_body<true>(n, p, g, m, v, state, hyper, 0.f, b1, b2, eps, 0.f, grad_scale, vec, copy_n, copy_src, copy_dst);
+    adam_step_body(n, p, g, m, v, state, hyper, b1, b2, eps, grad_scale, vec, copy_n, copy_src, copy_dst);
 }
 
 // The same pass confined to a chosen number of compute units (mmvae_adam_set_workgroups): that many workgroups of 1024
@@ -682,38 +670,23 @@ __global__ __launch_bounds__(256) void adam_step_hp_kernel(int64_t n, float* __r
 // another kernel whose grid is capped to the remaining units (the engine's deferred expert update).  Elementwise work:
 // identical results for any grid.
 constexpr int ADAM_WIDE_LDS = 84 * 1024;
-__global__ __launch_bounds__(1024) void adam_step_wide_kernel(int64_t n, float* __restrict__ p,
-                                                              const float* __restrict__ g, float* __restrict__ m,
-                                                              float* __restrict__ v, const float* __restrict__ state,
-                                                              float lr, float b1, float b2, float eps, float wd,
-                                                              float grad_scale, int vec, int copy_n,
-                                                              const float* copy_src, float* copy_dst) {
-    adam_step_body<false>(n, p, g, m, v, state, nullptr, lr, b1, b2, eps, wd, grad_scale, vec, copy_n, copy_src, copy_dst);
-}
 __global__ __launch_bounds__(1024) void adam_step_wide_hp_kernel(int64_t n, float* __restrict__ p,
                                                                  const float* __restrict__ g, float* __restrict__ m,
                                                                  float* __restrict__ v, const float* __restrict__ state,
                                                                  const float* __restrict__ hyper, float b1, float b2,
                                                                  float eps, float grad_scale, int vec, int copy_n,
                                                                  const float* copy_src, float* copy_dst) {
-    adam_step_body<true>(n, p, g, m, v, state, hyper, 0.f, b1, b2, eps, 0.f, grad_scale, vec, copy_n, copy_src, copy_dst);
+    adam_step_body(n, p, g, m, v, state, hyper, b1, b2, eps, grad_scale, vec, copy_n, copy_src, copy_dst);
 }
 
 // The update of several optimisers' arenas in one launch (blockIdx.y = arena): the adversaries of a step.  Arithmetic of
-// adam_step_kernel per arena.
-__global__ __launch_bounds__(256) void adam_step_multi_kernel(const mmvae_adam_arena* __restrict__ arenas) {
-    const mmvae_adam_arena a = arenas[blockIdx.y];
-    const uintptr_t al = reinterpret_cast<uintptr_t>(a.p) | reinterpret_cast<uintptr_t>(a.g) |
-                         reinterpret_cast<uintptr_t>(a.m) | reinterpret_cast<uintptr_t>(a.v);
-    adam_step_body<false>(a.n, a.p, a.g, a.m, a.v, a.state, nullptr, a.lr, a.beta1, a.beta2, a.eps, a.weight_decay,
-                          a.grad_scale, (al & 15u) == 0, 0, nullptr, nullptr);
-}
+// adam_step_hp_kernel per arena.
 __global__ __launch_bounds__(256) void adam_step_multi_hp_kernel(const mmvae_adam_arena_hp* __restrict__ arenas) {
     const mmvae_adam_arena_hp a = arenas[blockIdx.y];
     const uintptr_t al = reinterpret_cast<uintptr_t>(a.p) | reinterpret_cast<uintptr_t>(a.g) |
                          reinterpret_cast<uintptr_t>(a.m) | reinterpret_cast<uintptr_t>(a.v);
-    adam_step_body<true>(a.n, a.p, a.g, a.m, a.v, a.state, a.hyper, 0.f, a.beta1, a.beta2, a.eps, 0.f, a.grad_scale,
-                         (al & 15u) == 0, 0, nullptr, nullptr);
+    adam_step_body(a.n, a.p, a.g, a.m, a.v, a.state, a.hyper, a.beta1, a.beta2, a.eps, a.grad_scale, (al & 15u) == 0, 0,
+                   nullptr, nullptr);
 }
 
 inline int grid_for(int64_t n, int per_block, int cap);
@@ -728,26 +701,29 @@ extern "C" int mmvae_adam_set_workgroups(int workgroups) {
 
 extern "C" int mmvae_adam_get_workgroups(void) { return g_adam_workgroups; }
 
-// `chip` / `wide`: the by-value pair of kernels or the `_hp` pair (the template is instantiated once for each pair,
-// so each has its own `attr`).
-template <typename K, typename... Args>
-static int launch_adam_step(K chip, K wide, int64_t n, hipStream_t stream, Args... args) {
+static int launch_adam_step(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                            const float* state, const float* hyper, float beta1, float beta2, float eps,
+                            float grad_scale, int copy_n, const float* copy_src, float* copy_dst, hipStream_t stream) {
+    const int vec = aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq);
     if (g_adam_workgroups > 0) {
         static bool attr = false;
         if (!attr) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(wide), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    ADAM_WIDE_LDS) != hipSuccess)
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(adam_step_wide_hp_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, ADAM_WIDE_LDS) != hipSuccess)
                 return MMVAE_ERR_LAUNCH;
             attr = true;
         }
-        MMVAE_LAUNCH(wide, dim3(g_adam_workgroups), dim3(1024), (size_t)ADAM_WIDE_LDS, stream, n, args...);
+        MMVAE_LAUNCH(adam_step_wide_hp_kernel, dim3(g_adam_workgroups), dim3(1024), (size_t)ADAM_WIDE_LDS, stream, n, param,
+                     grad, exp_avg, exp_avg_sq, state, hyper, beta1, beta2, eps, grad_scale, vec, copy_n, copy_src,
+                     copy_dst);
     } else {
         // One workgroup per 1024 elements, no grid-stride loop: the hardware hands out workgroups in order, so the seven
         // streams of the pass (p, g, m, v in; p, m, v out) move through memory as one narrow window.  With the grid capped
         // at 4096 workgroups and a loop (r1-r3), the resident half of the grid and the half that waits for it drift apart
         // over the iterations: 42 M parameters 176-183 us against 166 (7.1 TB/s), 124 M (the reference's 60 530 genes)
         // 729 us against 578 (tools/debug/adam_bw.py); C2 step 0.980 -> 0.960 ms, 60 530 / 52 437 genes 2.49 -> 2.36.
-        MMVAE_LAUNCH(chip, dim3(grid_for(n, 1024, STREAM_GRID_CAP)), dim3(256), 0, stream, n, args...);
+        MMVAE_LAUNCH(adam_step_hp_kernel, dim3(grid_for(n, 1024, STREAM_GRID_CAP)), dim3(256), 0, stream, n, param, grad,
+                     exp_avg, exp_avg_sq, state, hyper, beta1, beta2, eps, grad_scale, vec, copy_n, copy_src, copy_dst);
     }
     MMVAE_LAUNCH_CHECK();
     return MMVAE_OK;
@@ -757,16 +733,15 @@ static int launch_adam_step(K chip, K wide, int64_t n, hipStream_t stream, Args.
 // one parameter tensor, with that tensor's own bias corrections): the optimiser of a conditional-layer model updates
 // only the condition blocks that took part in the step (torch.optim.Adam skips parameters without a gradient and counts
 // steps per parameter) -- hundreds of 128 x 128 blocks out of thousands -- in ONE launch.
-template <bool HP>
 __device__ __forceinline__ void adam_step_jobs_body(const mmvae_adam_job* __restrict__ jobs, float* __restrict__ p,
                                                     const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, const float* __restrict__ state,
-                                                    const float* __restrict__ hyper, float lr, float b1, float b2,
-                                                    float eps, float wd, float grad_scale) {
+                                                    const float* __restrict__ hyper, float b1, float b2, float eps,
+                                                    float grad_scale) {
     const mmvae_adam_job job = jobs[blockIdx.x];
     if ((job.reserved & 3) == 2) return;  // a retired segment (zeroed for the exchange, takes no step)
-    float decay;
-    adam_hyper<HP>(hyper, lr, wd, decay);
+    float lr, wd, decay;
+    adam_hyper(hyper, lr, wd, decay);
     const float gmul = state[2] * grad_scale;
     const float step_size = lr / job.bc1;
     const float inv_bc2_sqrt = 1.f / sqrtf(job.bc2);
@@ -784,7 +759,7 @@ __device__ __forceinline__ void adam_step_jobs_body(const mmvae_adam_job* __rest
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float pe = pp[e], me = mm[e], ve = vw[e];
-                adam_elem<HP>(pe, gg[e], me, ve, gmul, wd, decay, b1, b2, step_size, inv_bc2_sqrt, eps, cv);
+                adam_elem(pe, gg[e], me, ve, gmul, wd, decay, b1, b2, step_size, inv_bc2_sqrt, eps, cv);
                 pp[e] = pe;
                 mm[e] = me;
                 vw[e] = ve;
@@ -794,27 +769,20 @@ __device__ __forceinline__ void adam_step_jobs_body(const mmvae_adam_job* __rest
             vv[i] = vw;
         }
         for (int i = 4 * nv + threadIdx.x; i < n; i += 256)
-            adam_elem<HP>(p[o + i], g[o + i], m[o + i], v[o + i], gmul, wd, decay, b1, b2, step_size, inv_bc2_sqrt, eps, cv);
+            adam_elem(p[o + i], g[o + i], m[o + i], v[o + i], gmul, wd, decay, b1, b2, step_size, inv_bc2_sqrt, eps, cv);
     } else {
         for (int i = threadIdx.x; i < n; i += 256)
-            adam_elem<HP>(p[o + i], g[o + i], m[o + i], v[o + i], gmul, wd, decay, b1, b2, step_size, inv_bc2_sqrt, eps, cv);
+            adam_elem(p[o + i], g[o + i], m[o + i], v[o + i], gmul, wd, decay, b1, b2, step_size, inv_bc2_sqrt, eps, cv);
     }
 }
 
-__global__ __launch_bounds__(256) void adam_step_jobs_kernel(const mmvae_adam_job* __restrict__ jobs, float* __restrict__ p,
-                                                             const float* __restrict__ g, float* __restrict__ m,
-                                                             float* __restrict__ v, const float* __restrict__ state,
-                                                             float lr, float b1, float b2, float eps, float wd,
-                                                             float grad_scale) {
-    adam_step_jobs_body<false>(jobs, p, g, m, v, state, nullptr, lr, b1, b2, eps, wd, grad_scale);
-}
 __global__ __launch_bounds__(256) void adam_step_jobs_hp_kernel(const mmvae_adam_job* __restrict__ jobs,
                                                                 float* __restrict__ p, const float* __restrict__ g,
                                                                 float* __restrict__ m, float* __restrict__ v,
                                                                 const float* __restrict__ state,
                                                                 const float* __restrict__ hyper, float b1, float b2,
                                                                 float eps, float grad_scale) {
-    adam_step_jobs_body<true>(jobs, p, g, m, v, state, hyper, 0.f, b1, b2, eps, 0.f, grad_scale);
+    adam_step_jobs_body(jobs, p, g, m, v, state, hyper, b1, b2, eps, grad_scale);
 }
 
 // Sum of squares of one job's arena segment -> partials[job] (0 for an empty job): the global norm of a step in which
@@ -1280,33 +1248,12 @@ extern "C" int mmvae_grad_sqnorm_ranges_prepare(int n_ranges, const float* const
     return MMVAE_OK;
 }
 
-extern "C" int mmvae_adam_step(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
-                               const float* state, float lr, float beta1, float beta2, float eps, float weight_decay,
-                               float grad_scale, mmvae_stream_t stream) {
-    if (n <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !state) return MMVAE_ERR_ARG;
-    const int vec = aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq);
-    return launch_adam_step(adam_step_kernel, adam_step_wide_kernel, n, (hipStream_t)stream, param, grad, exp_avg,
-                            exp_avg_sq, state, lr, beta1, beta2, eps, weight_decay, grad_scale, vec, 0,
-                            (const float*)nullptr, (float*)nullptr);
-}
-
 extern "C" int mmvae_adam_step_hp(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                                   const float* state, const float* hyper, float beta1, float beta2, float eps,
                                   float grad_scale, mmvae_stream_t stream) {
     if (n <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !state || !hyper) return MMVAE_ERR_ARG;
-    const int vec = aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq);
-    return launch_adam_step(adam_step_hp_kernel, adam_step_wide_hp_kernel, n, (hipStream_t)stream, param, grad, exp_avg,
-                            exp_avg_sq, state, hyper, beta1, beta2, eps, grad_scale, vec, 0, (const float*)nullptr,
-                            (float*)nullptr);
-}
-
-extern "C" int mmvae_adam_step_multi(int n_arenas, const mmvae_adam_arena* arenas_dev, int64_t max_n,
-                                     mmvae_stream_t stream) {
-    if (n_arenas < 1 || n_arenas > 64 || !arenas_dev || max_n <= 0) return MMVAE_ERR_ARG;
-    MMVAE_LAUNCH(adam_step_multi_kernel, dim3(grid_for(max_n, 1024, 4096), n_arenas), dim3(256), 0, (hipStream_t)stream,
-                 arenas_dev);
-    MMVAE_LAUNCH_CHECK();
-    return MMVAE_OK;
+    return launch_adam_step(n, param, grad, exp_avg, exp_avg_sq, state, hyper, beta1, beta2, eps, grad_scale, 0, nullptr,
+                            nullptr, (hipStream_t)stream);
 }
 
 extern "C" int mmvae_adam_step_multi_hp(int n_arenas, const mmvae_adam_arena_hp* arenas_dev, int64_t max_n,
@@ -1318,37 +1265,14 @@ extern "C" int mmvae_adam_step_multi_hp(int n_arenas, const mmvae_adam_arena_hp*
     return MMVAE_OK;
 }
 
-extern "C" int mmvae_adam_step_copy(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
-                                    const float* state, float lr, float beta1, float beta2, float eps,
-                                    float weight_decay, float grad_scale, int copy_n, const float* copy_src,
-                                    float* copy_dst, mmvae_stream_t stream) {
-    if (n <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !state) return MMVAE_ERR_ARG;
-    if (copy_n < 0 || copy_n > 65536 || (copy_n > 0 && (!copy_src || !copy_dst))) return MMVAE_ERR_ARG;
-    const int vec = aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq);
-    return launch_adam_step(adam_step_kernel, adam_step_wide_kernel, n, (hipStream_t)stream, param, grad, exp_avg,
-                            exp_avg_sq, state, lr, beta1, beta2, eps, weight_decay, grad_scale, vec, copy_n, copy_src,
-                            copy_dst);
-}
-
 extern "C" int mmvae_adam_step_copy_hp(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                                        const float* state, const float* hyper, float beta1, float beta2, float eps,
                                        float grad_scale, int copy_n, const float* copy_src, float* copy_dst,
                                        mmvae_stream_t stream) {
     if (n <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !state || !hyper) return MMVAE_ERR_ARG;
     if (copy_n < 0 || copy_n > 65536 || (copy_n > 0 && (!copy_src || !copy_dst))) return MMVAE_ERR_ARG;
-    const int vec = aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq);
-    return launch_adam_step(adam_step_hp_kernel, adam_step_wide_hp_kernel, n, (hipStream_t)stream, param, grad, exp_avg,
-                            exp_avg_sq, state, hyper, beta1, beta2, eps, grad_scale, vec, copy_n, copy_src, copy_dst);
-}
-
-extern "C" int mmvae_adam_step_jobs(int n_jobs, const mmvae_adam_job* jobs_dev, float* param, const float* grad,
-                                    float* exp_avg, float* exp_avg_sq, const float* state, float lr, float beta1,
-                                    float beta2, float eps, float weight_decay, float grad_scale, mmvae_stream_t stream) {
-    if (n_jobs <= 0 || !jobs_dev || !param || !grad || !exp_avg || !exp_avg_sq || !state) return MMVAE_ERR_ARG;
-    MMVAE_LAUNCH(adam_step_jobs_kernel, dim3(n_jobs), dim3(256), 0, (hipStream_t)stream, jobs_dev, param, grad, exp_avg,
-                 exp_avg_sq, state, lr, beta1, beta2, eps, weight_decay, grad_scale);
-    MMVAE_LAUNCH_CHECK();
-    return MMVAE_OK;
+    return launch_adam_step(n, param, grad, exp_avg, exp_avg_sq, state, hyper, beta1, beta2, eps, grad_scale, copy_n,
+                            copy_src, copy_dst, (hipStream_t)stream);
 }
 
 extern "C" int mmvae_adam_step_jobs_hp(int n_jobs, const mmvae_adam_job* jobs_dev, float* param, const float* grad,

@@ -627,13 +627,12 @@ def sqnorm_partials(n: int) -> int:
     return _lib.load().mmvae_sqnorm_partials(n)
 
 
-def clip_adam_step(param, grad, exp_avg, exp_avg_sq, state, partials, *, lr=5e-3, beta1=0.9, beta2=0.999, eps=1e-8,
-                   weight_decay=1e-6, max_norm=0.0, grad_scale=1.0, do_norm=True, do_step=True, advance=True,
-                   hyper=None):
+def clip_adam_step(param, grad, exp_avg, exp_avg_sq, state, partials, *, beta1=0.9, beta2=0.999, eps=1e-8,
+                   max_norm=0.0, grad_scale=1.0, do_norm=True, do_step=True, advance=True, hyper=None):
     """Global-norm clip + Adam over one flat arena.  `state`: float32[8] device tensor (step, norm, clip, bc1, bc2).
     do_norm: recompute the gradient norm; advance: increment the step counter; do_step: apply the update.
-    `hyper`: float32[4] device tensor (lr, weight_decay, decoupled 0 / 1, 0) read by the update in place of `lr` and
-    `weight_decay` (mmvae_adam_step_hp); decoupled = 1 is torch.optim.AdamW's rule."""
+    `hyper`: float32[4] device tensor (lr, weight_decay, decoupled 0 / 1, 0) read by the update (mmvae_adam_step_hp);
+    decoupled = 1 is torch.optim.AdamW's rule.  Required when do_step is true."""
     lib = _lib.load()
     for n_, t in (("param", param), ("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq),
                   ("state", state), ("partials", partials)):
@@ -643,6 +642,8 @@ def clip_adam_step(param, grad, exp_avg, exp_avg_sq, state, partials, *, lr=5e-3
     n = param.numel()
     if grad.numel() != n or exp_avg.numel() != n or exp_avg_sq.numel() != n or state.numel() < 8:
         raise ValueError("arena sizes")
+    if do_step and hyper is None:
+        raise ValueError("hyper (float32[4] device tensor: lr, weight_decay, decoupled, 0) is required when do_step is true")
     if hyper is not None:
         _chk(hyper, "hyper")
         if not hyper.is_contiguous() or hyper.numel() < _lib.ADAM_HYPER_FLOATS:
@@ -656,12 +657,9 @@ def clip_adam_step(param, grad, exp_avg, exp_avg_sq, state, partials, *, lr=5e-3
     flags = (_lib.PREPARE_NORM if do_norm else 0) | (_lib.PREPARE_ADVANCE if (advance and do_step) else 0)
     _lib.check(lib.mmvae_adam_prepare(npart, _ptr(partials), float(max_norm), float(grad_scale), beta1, beta2,
                                       _ptr(state), flags, s), "mmvae_adam_prepare")
-    if do_step and hyper is not None:
+    if do_step:
         _lib.check(lib.mmvae_adam_step_hp(n, _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(state),
                                           _ptr(hyper), beta1, beta2, eps, float(grad_scale), s), "mmvae_adam_step_hp")
-    elif do_step:
-        _lib.check(lib.mmvae_adam_step(n, _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(state), lr,
-                                       beta1, beta2, eps, weight_decay, float(grad_scale), s), "mmvae_adam_step")
 
 
 def philox_keep_mask(shape, p_drop: float, rng_state: torch.Tensor, stream_id: int = 0, advance: bool = True,

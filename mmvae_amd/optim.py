@@ -373,36 +373,22 @@ class HipAdam(torch.optim.Optimizer):
         parameters without a gradient are left untouched (no moment decay, no weight decay) and every parameter uses
         the bias corrections of its OWN step count.  The global norm / clip coefficient come from the whole arena (the
         skipped slices are zero); the update runs over a job table of the tensors that took part, in one launch
-        (mmvae_adam_step_jobs)."""
+        (mmvae_adam_step_jobs_hp)."""
         import numpy as np
 
         a = self.arena
-        n = len(a.params)
-        if self._steps is None:
-            self._steps = np.full(n, int(round(float(self.state_dev[0]))), dtype=np.int64)
+        steps = self.host_steps()
         skip = set(self._inactive)
+        active = np.setdiff1d(np.arange(len(a.params)), np.fromiter(skip, dtype=np.int64, count=len(skip)),
+                              assume_unique=True)
         if self._hip:
             # norm (unless compute_grad_norm() just produced it) and the clip coefficient for the CURRENT max_grad_norm
             # (Lightning sets the clip value between the norm logging and the step)
             ops.clip_adam_step(a.data, a.grad, a.exp_avg, a.exp_avg_sq, self.state_dev, self.partials, beta1=b1,
                                beta2=b2, max_norm=self.max_grad_norm or 0.0, grad_scale=self.grad_scale,
                                do_norm=not norm_valid, do_step=False)
-            norm, clip = self.state_dev[1], self.state_dev[2]
-        else:
-            grad = a.grad * self.grad_scale
-            norm = grad.norm()
-            clip = 1.0
-            if self.max_grad_norm:
-                clip = min(1.0, float(self.max_grad_norm) / (float(norm) + 1e-6))
-            self.state_dev[1], self.state_dev[2] = norm, clip
-        active = np.setdiff1d(np.arange(n), np.fromiter(skip, dtype=np.int64, count=len(skip)), assume_unique=True)
-        steps = np.asarray(self._steps, dtype=np.int64)
-        t_act = steps[active] + 1
-        bc1 = (np.float32(1.0) - np.power(np.float32(b1), t_act.astype(np.float32))).astype(np.float32)
-        bc2 = (np.float32(1.0) - np.power(np.float32(b2), t_act.astype(np.float32))).astype(np.float32)
-        if self._hip:
             # one launch for every tensor that took part: a job per <= 16384-element chunk, carrying the tensor's own
-            # bias corrections (mmvae_adam_step_jobs)
+            # bias corrections
             from . import _lib
 
             jobs = self.job_table(active, b1, b2)
@@ -416,47 +402,46 @@ class HipAdam(torch.optim.Optimizer):
             _lib.check(rc, "mmvae_adam_step_jobs_hp")
             self._keep_jobs = jobs_dev  # outlives the launch
         else:
+            norm = (a.grad * self.grad_scale).norm()
+            clip = 1.0
+            if self.max_grad_norm:
+                clip = min(1.0, float(self.max_grad_norm) / (float(norm) + 1e-6))
+            self.state_dev[1], self.state_dev[2] = norm, clip
+            t_act = steps[active] + 1
+            bc1 = (np.float32(1.0) - np.power(np.float32(b1), t_act.astype(np.float32))).astype(np.float32)
+            bc2 = (np.float32(1.0) - np.power(np.float32(b2), t_act.astype(np.float32))).astype(np.float32)
             for j, i in enumerate(active):
-                p, o = a.params[i], a.offsets[i]
-                sl = slice(o, o + p.numel())
-                gr = a.grad[sl] * self.grad_scale * float(clip)
-                if getattr(self, "clip_value", None):  # gradient_clip_algorithm "value" (config.py:8)
-                    gr = gr.clamp(-self.clip_value, self.clip_value)
-                if self.decoupled_weight_decay:  # torch.optim.AdamW: the parameter decays, the gradient carries no wd * p
-                    a.data[sl].mul_(1 - g["lr"] * g["weight_decay"])
-                else:
-                    gr = gr + g["weight_decay"] * a.data[sl]
-                a.exp_avg[sl].lerp_(gr, 1 - b1)
-                a.exp_avg_sq[sl].mul_(b2).addcmul_(gr, gr, value=1 - b2)
-                denom = a.exp_avg_sq[sl].sqrt() / (float(bc2[j]) ** 0.5) + g["eps"]
-                a.data[sl].addcdiv_(a.exp_avg[sl], denom, value=-g["lr"] / float(bc1[j]))
-        steps[active] = t_act
-        self._steps = steps
-        self.state_dev[0] = float(self._steps.max())
+                o = a.offsets[i]
+                self._adam_cpu_plumbing(g, b1, b2, slice(o, o + a.params[i].numel()), clip, float(bc1[j]), float(bc2[j]))
+        steps[active] += 1
+        self.state_dev[0] = float(steps.max())
         self._norm_valid = False
+
+    def _adam_cpu_plumbing(self, g, b1, b2, sl, clip, bc1, bc2):
+        """torch.optim.Adam / AdamW over the slice `sl` of the arenas, with the bias corrections of its step count."""
+        a = self.arena
+        gr = a.grad[sl] * self.grad_scale * float(clip)
+        if getattr(self, "clip_value", None):  # gradient_clip_algorithm "value" (config.py:8)
+            gr = gr.clamp(-self.clip_value, self.clip_value)
+        if self.decoupled_weight_decay:  # torch.optim.AdamW: the parameter decays, the gradient carries no wd * p
+            a.data[sl].mul_(1 - g["lr"] * g["weight_decay"])
+        else:
+            gr = gr + g["weight_decay"] * a.data[sl]
+        a.exp_avg[sl].lerp_(gr, 1 - b1)
+        a.exp_avg_sq[sl].mul_(b2).addcmul_(gr, gr, value=1 - b2)
+        denom = a.exp_avg_sq[sl].sqrt() / (bc2 ** 0.5) + g["eps"]
+        a.data[sl].addcdiv_(a.exp_avg[sl], denom, value=-g["lr"] / bc1)
 
     def _step_cpu_plumbing(self, g, b1, b2):
         a = self.arena
-        grad = a.grad * self.grad_scale
-        norm = grad.norm()
+        norm = (a.grad * self.grad_scale).norm()
         clip = 1.0
         if self.max_grad_norm:
             clip = min(1.0, float(self.max_grad_norm) / (float(norm) + 1e-6))
         self.state_dev[0] += 1
         t = float(self.state_dev[0])
         self.state_dev[1], self.state_dev[2] = norm, clip
-        grad = grad * clip
-        if getattr(self, "clip_value", None):
-            grad = grad.clamp(-self.clip_value, self.clip_value)
-        if self.decoupled_weight_decay:  # torch.optim.AdamW: the parameter decays, the gradient carries no wd * p
-            a.data.mul_(1 - g["lr"] * g["weight_decay"])
-        else:
-            grad = grad + g["weight_decay"] * a.data
-        a.exp_avg.lerp_(grad, 1 - b1)
-        a.exp_avg_sq.mul_(b2).addcmul_(grad, grad, value=1 - b2)
-        bc1, bc2 = 1 - b1 ** t, 1 - b2 ** t
-        denom = a.exp_avg_sq.sqrt() / (bc2 ** 0.5) + g["eps"]
-        a.data.addcdiv_(a.exp_avg, denom, value=-g["lr"] / bc1)
+        self._adam_cpu_plumbing(g, b1, b2, slice(0, a.numel), clip, 1 - b1 ** t, 1 - b2 ** t)
 
     # ---- checkpoint surface compatible with torch.optim.Adam's per-parameter state
     def _settle(self) -> None:

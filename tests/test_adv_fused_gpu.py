@@ -1,4 +1,4 @@
-"""Row-owner adversary kernels (mmvae_adv_pass_f32 / mmvae_adv_dw_f32 / mmvae_adam_step_multi) through the C-ABI against
+"""Row-owner adversary kernels (mmvae_adv_pass_f32 / mmvae_adv_dw_f32 / mmvae_adam_step_multi_hp) through the C-ABI against
 torch autograd in fp64 on the CPU: one adversarial phase of `CMMVAEModel.grf` (reference models/cmmvae_model.py:59-101;
 Adversarial, GradientReversalFunction: modules/base/components.py:638-674, 879-899) -- encoder FCBlock (Linear -> ReLU
 -> Dropout), every head, CrossEntropyLoss(sum), gradients of every parameter and of the hidden representation.
@@ -28,7 +28,7 @@ class _Pool:
 
 
 class _FakeOpt:
-    """What AdvProgram needs of a HipAdam: flat arenas, state words, one param group."""
+    """What AdvProgram needs of a HipAdam: flat arenas, state words, hyper words {lr, wd, 0, 0}, one param group."""
 
     def __init__(self, numel, device):
         class A:
@@ -42,6 +42,8 @@ class _FakeOpt:
         self.arena.exp_avg_sq = torch.zeros(numel, device=device)
         self.state_dev = torch.zeros(8, device=device)
         self.param_groups = [dict(lr=5e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-6)]
+        g = self.param_groups[0]
+        self.hyper_dev = torch.tensor([g["lr"], g["weight_decay"], 0.0, 0.0], device=device)
 
 
 def _build(widths, classes, B, seed, p_drop, device):
@@ -193,7 +195,7 @@ def test_adv_pass_and_dw_match_autograd(widths, classes, B, p_drop, reverse):
 
 def test_adv_two_jobs_one_launch_and_adam_multi():
     """Two adversaries (C4's) as two jobs of the same launches: each equals its single-job run bit for bit; total_loss
-    accumulates in job order; mmvae_adam_step_multi equals mmvae_adam_step per arena bit for bit."""
+    accumulates in job order; mmvae_adam_step_multi_hp equals mmvae_adam_step_hp per arena bit for bit."""
     from mmvae_amd import _lib
     from mmvae_amd.adv_program import AdvProgram
 
@@ -239,9 +241,9 @@ def test_adv_two_jobs_one_launch_and_adam_multi():
         p, gr, st = before[i]
         mm, vv = torch.zeros_like(p), torch.zeros_like(p)
         gp = nt.opt.param_groups[0]
-        _lib.check(lib.mmvae_adam_step(p.numel(), p.data_ptr(), gr.data_ptr(), mm.data_ptr(), vv.data_ptr(), st.data_ptr(),
-                                       gp["lr"], gp["betas"][0], gp["betas"][1], gp["eps"], gp["weight_decay"], 1.0,
-                                       torch.cuda.current_stream().cuda_stream), "mmvae_adam_step")
+        _lib.check(lib.mmvae_adam_step_hp(p.numel(), p.data_ptr(), gr.data_ptr(), mm.data_ptr(), vv.data_ptr(),
+                                          st.data_ptr(), nt.opt.hyper_dev.data_ptr(), gp["betas"][0], gp["betas"][1],
+                                          gp["eps"], 1.0, torch.cuda.current_stream().cuda_stream), "mmvae_adam_step_hp")
         torch.cuda.synchronize()
         assert torch.equal(p, nt.opt.arena.data)
         assert torch.equal(mm, nt.opt.arena.exp_avg) and torch.equal(vv, nt.opt.arena.exp_avg_sq)

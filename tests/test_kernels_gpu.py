@@ -457,11 +457,12 @@ def test_clip_adam_matches_torch(ops):
     p, m, v = dev(p0.clone()), torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")
     state = torch.zeros(8, device="cuda")
     partials = torch.empty(ops.sqnorm_partials(n), device="cuda")
+    hyper = torch.tensor([5e-3, 1e-6, 0.0, 0.0], device="cuda")
     for g in (g1, g2):
         pt.grad = g.clone()
         norm = torch.nn.utils.clip_grad_norm_([pt], 10.0)
         opt.step()
-        ops.clip_adam_step(p, dev(g), m, v, state, partials, max_norm=10.0)
+        ops.clip_adam_step(p, dev(g), m, v, state, partials, max_norm=10.0, hyper=hyper)
         assert abs(float(state[1]) - float(norm)) <= 1e-5 * float(norm)
         assert rel_l2(p, pt.detach()) < 1e-6
     assert float(state[0]) == 2.0
@@ -479,6 +480,7 @@ def test_adam_confined_to_n_compute_units_is_bit_identical(ops):
     n = 1_000_003
     s = torch.cuda.current_stream().cuda_stream
     state = torch.tensor([4.0, 0, 0.7, 0.9, 0.95, 0.0, 0, 0], device="cuda")  # step, norm, clip, bias corrections, clip value
+    hyper = torch.tensor([5e-3, 1e-6, 0.0, 0.0], device="cuda")
     outs = []
     try:
         for wg in (0, 7, 64):
@@ -486,8 +488,8 @@ def test_adam_confined_to_n_compute_units_is_bit_identical(ops):
             p, g = dev(rnd(n, seed=1)), dev(rnd(n, seed=2, scale=0.1))
             m, v = dev(rnd(n, seed=3, scale=0.01)), dev(rnd(n, seed=4, scale=0.01)).abs()
             src, dst = dev(rnd(256, seed=5)), torch.zeros(256, device="cuda")
-            rc = lib.mmvae_adam_step_copy(n, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), state.data_ptr(),
-                                          5e-3, 0.9, 0.999, 1e-8, 1e-6, 0.5, 256, src.data_ptr(), dst.data_ptr(), s)
+            rc = lib.mmvae_adam_step_copy_hp(n, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), state.data_ptr(),
+                                             hyper.data_ptr(), 0.9, 0.999, 1e-8, 0.5, 256, src.data_ptr(), dst.data_ptr(), s)
             assert rc == 0
             assert torch.equal(dst, src)
             outs.append((p, m, v))

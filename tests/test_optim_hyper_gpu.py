@@ -1,7 +1,8 @@
 """The optimiser's learning rate, weight decay and decay mode as device words (`_hp` entry points of include/mmvae_hip.h,
-HipAdam.hyper_dev): bit-identity with the by-value entries in coupled mode, torch.optim.AdamW's rule in decoupled mode,
-a captured graph that follows the words, and the step engine under per-step schedules -- against the module path,
-without rebuilding its programs, with `optim_cls="AdamW"` models taken by the engine, and on the sharded update."""
+HipAdam.hyper_dev): bit-identity with the recorded results of the retired by-value entries in coupled mode,
+torch.optim.AdamW's rule in decoupled mode, a captured graph that follows the words, and the step engine under per-step
+schedules -- against the module path, without rebuilding its programs, with `optim_cls="AdamW"` models taken by the
+engine, and on the sharded update."""
 import os
 import tempfile
 import warnings
@@ -60,32 +61,58 @@ def _views(full, n, offset):
     return [t[offset:offset + n] for t in full]
 
 
+# The by-value entry points (the step, its copy rider, the job list and the multi-arena launch with lr and weight decay
+# as launch arguments) left the library with ABI 14.  What they produced at ABI 13 for exactly the inputs built below is
+# recorded in tests/golden/adam_by_value.npz (tests/golden/make_adam_golden.py, which also proved the ABI 13 `_hp`
+# entries bit-identical to them in the same run).
+JOB_N = 50_000
+JOB_SEGS = [(0, 1, 0), (5, 16384, 0), (16392, 100, 2), (16500, 16384, 0), (40_000, 4099, 0)]  # offset, len, flag
+MULTI_SIZES = [(4099, 0, 5e-3, 1e-2), (1027, 1, 1e-3, 0.0)]  # n, offset, lr, weight decay
+MULTI_CV = (0.0, 0.05)
+
+
+def _job_table():
+    from mmvae_amd.optim import HipAdam
+
+    jobs = np.zeros(len(JOB_SEGS), dtype=np.dtype(HipAdam.JOB_DTYPE))
+    for j, (o, ln, f) in enumerate(JOB_SEGS):
+        assert o + ln <= JOB_N
+        jobs[j]["offset"], jobs[j]["len"], jobs[j]["bc1"], jobs[j]["bc2"], jobs[j]["reserved"] = o, ln, 0.1 + 0.1 * j, 0.001 * (j + 1), f
+    return torch.from_numpy(jobs.view(np.uint8)).cuda()
+
+
+@pytest.fixture(scope="module")
+def by_value():
+    with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "adam_by_value.npz")) as z:
+        out = {k: torch.from_numpy(z[k]).cuda() for k in z.files}
+    assert all(t.dtype == torch.float32 for t in out.values())
+    return out
+
+
 @pytest.mark.parametrize("n,offset", [(4099, 0), (4099, 1), (3, 0)], ids=["vector+tail", "scalar", "n3"])
 @pytest.mark.parametrize("cv", [0.0, 0.05], ids=["norm", "value"])
-def test_hp_equals_by_value_bit_for_bit(lib, n, offset, cv):
-    """hyper = {lr, wd, 0, 0}: the bits of mmvae_adam_step -- 16-byte body + 3-element tail, the scalar path of
-    unaligned arenas, fewer elements than one 16-byte group -- and nothing written outside [0, n)."""
+def test_hp_equals_by_value_bit_for_bit(lib, by_value, n, offset, cv):
+    """hyper = {lr, wd, 0, 0}: the recorded bits of the by-value step -- 16-byte body + 3-element tail, the scalar path of
+    unaligned arenas (a record of its own: the two loops do not round alike), fewer elements than one
+    16-byte group -- and nothing written outside [0, n)."""
     state = _state(cv)
-    ref, got = _arenas(n, offset), _arenas(n, offset)
-    p, g, m, v = _views(ref, n, offset)
-    assert (p.data_ptr() % 16 == 0) == (offset == 0)
-    assert lib.mmvae_adam_step(n, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), state.data_ptr(), LR, B1, B2, EPS,
-                               WD, GS, _stream()) == 0
+    got = _arenas(n, offset)
     p, g, m, v = _views(got, n, offset)
+    assert (p.data_ptr() % 16 == 0) == (offset == 0)
     assert lib.mmvae_adam_step_hp(n, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), state.data_ptr(),
                                   _hyper().data_ptr(), B1, B2, EPS, GS, _stream()) == 0
     torch.cuda.synchronize()
     fresh = _arenas(n, offset)
-    for a, b, f in zip(ref, got, fresh):
-        assert torch.equal(a, b)
+    for name, t in zip("pmv", (p, m, v)):
+        assert torch.equal(t, by_value[f"step_n{n}_off{offset}_cv{cv:g}_{name}"]), name
     assert not torch.equal(got[0], fresh[0]) and torch.equal(got[1], fresh[1])  # it stepped; the gradient is read only
     for t, f in zip(got, fresh):  # the padding around the arena is untouched
         assert torch.equal(t[:offset], f[:offset]) and torch.equal(t[offset + n:], f[offset + n:])
 
 
-def test_hp_copy_rider_and_confined_grid_equal_by_value(lib):
-    """mmvae_adam_step_copy_hp on the chip-filling grid and on 7 fat workgroups (mmvae_adam_set_workgroups): the bits of
-    mmvae_adam_step_copy, and the rider's words copied."""
+def test_hp_copy_rider_and_confined_grid_equal_by_value(lib, by_value):
+    """mmvae_adam_step_copy_hp on the chip-filling grid and on 7 fat workgroups (mmvae_adam_set_workgroups): the recorded
+    bits of the by-value step (its rider form gave the same), and the rider's words copied."""
     n = 4099
     state = _state()
     src = _rnd(256, 5).cuda()
@@ -93,54 +120,42 @@ def test_hp_copy_rider_and_confined_grid_equal_by_value(lib):
     try:
         for wg in (0, 7):
             assert lib.mmvae_adam_set_workgroups(wg) == 0
-            for hp in (False, True):
-                p, g, m, v = _arenas(n)
-                dst = torch.zeros(256, device="cuda")
-                if hp:
-                    rc = lib.mmvae_adam_step_copy_hp(n, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
-                                                     state.data_ptr(), _hyper().data_ptr(), B1, B2, EPS, GS, 256,
-                                                     src.data_ptr(), dst.data_ptr(), _stream())
-                else:
-                    rc = lib.mmvae_adam_step_copy(n, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
-                                                  state.data_ptr(), LR, B1, B2, EPS, WD, GS, 256, src.data_ptr(),
-                                                  dst.data_ptr(), _stream())
-                assert rc == 0
-                torch.cuda.synchronize()
-                assert torch.equal(dst, src), (wg, hp)
-                outs.append((p, m, v))
+            p, g, m, v = _arenas(n)
+            dst = torch.zeros(256, device="cuda")
+            assert lib.mmvae_adam_step_copy_hp(n, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), state.data_ptr(),
+                                               _hyper().data_ptr(), B1, B2, EPS, GS, 256, src.data_ptr(), dst.data_ptr(),
+                                               _stream()) == 0
+            torch.cuda.synchronize()
+            assert torch.equal(dst, src), wg
+            assert torch.equal(g, _arenas(n)[1]), wg
+            outs.append((p, m, v))
     finally:
         lib.mmvae_adam_set_workgroups(0)
-    for p, m, v in outs[1:]:
-        assert torch.equal(p, outs[0][0]) and torch.equal(m, outs[0][1]) and torch.equal(v, outs[0][2])
+    for out in outs:
+        for name, t in zip("pmv", out):
+            assert torch.equal(t[:n], by_value[f"step_n{n}_off0_cv0_{name}"]), name
+            assert torch.equal(t, outs[0]["pmv".index(name)])  # confined grid == chip-filling grid, padding included
     assert not torch.equal(outs[0][0], _arenas(n)[0])
 
 
-def test_hp_jobs_equal_by_value(lib):
+def test_hp_jobs_equal_by_value(lib, by_value):
     """mmvae_adam_step_jobs_hp: jobs at offsets 0 (16-byte path) and 5 (scalar path), lengths 1 and 16 384, a full
-    aligned job and a retired one -- the bits of mmvae_adam_step_jobs; retired and unlisted elements untouched."""
-    from mmvae_amd.optim import HipAdam
-
-    n = 50_000
-    segs = [(0, 1, 0), (5, 16384, 0), (16392, 100, 2), (16500, 16384, 0), (40_000, 4099, 0)]  # offset, len, flag
-    jobs = np.zeros(len(segs), dtype=np.dtype(HipAdam.JOB_DTYPE))
-    for j, (o, ln, f) in enumerate(segs):
-        assert o + ln <= n
-        jobs[j]["offset"], jobs[j]["len"], jobs[j]["bc1"], jobs[j]["bc2"], jobs[j]["reserved"] = o, ln, 0.1 + 0.1 * j, 0.001 * (j + 1), f
-    jobs_dev = torch.from_numpy(jobs.view(np.uint8)).cuda()
+    aligned job and a retired one -- the recorded bits of the by-value job launch; retired and unlisted elements
+    untouched."""
+    n = JOB_N
+    jobs_dev = _job_table()
     state = _state()
-    ref, got = _arenas(n), _arenas(n)
-    p, g, m, v = ref
-    assert lib.mmvae_adam_step_jobs(len(segs), jobs_dev.data_ptr(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
-                                    state.data_ptr(), LR, B1, B2, EPS, WD, GS, _stream()) == 0
+    got = _arenas(n)
     p, g, m, v = got
-    assert lib.mmvae_adam_step_jobs_hp(len(segs), jobs_dev.data_ptr(), p.data_ptr(), g.data_ptr(), m.data_ptr(),
+    assert lib.mmvae_adam_step_jobs_hp(len(JOB_SEGS), jobs_dev.data_ptr(), p.data_ptr(), g.data_ptr(), m.data_ptr(),
                                        v.data_ptr(), state.data_ptr(), _hyper().data_ptr(), B1, B2, EPS, GS, _stream()) == 0
     torch.cuda.synchronize()
-    for a, b in zip(ref, got):
-        assert torch.equal(a, b)
+    for name, t in zip("pmv", (p, m, v)):
+        assert torch.equal(t[:n], by_value[f"jobs_{name}"]), name
     fresh = _arenas(n)
+    assert torch.equal(g, fresh[1])
     touched = torch.zeros(n + 8, dtype=torch.bool, device="cuda")
-    for o, ln, f in segs:
+    for o, ln, f in JOB_SEGS:
         if f != 2:
             touched[o:o + ln] = True
     for t, f in zip((got[0], got[2], got[3]), (fresh[0], fresh[2], fresh[3])):
@@ -148,38 +163,35 @@ def test_hp_jobs_equal_by_value(lib):
         assert not (t[touched] == f[touched]).all()
 
 
-def test_hp_multi_equals_by_value(lib):
-    """mmvae_adam_step_multi_hp over two arenas (one unaligned, each with its own hyper words) against
-    mmvae_adam_step_multi."""
+def test_hp_multi_equals_by_value(lib, by_value):
+    """mmvae_adam_step_multi_hp over two arenas (one unaligned, each with its own hyper words) against the recorded bits
+    of the by-value multi-arena launch."""
+    import ctypes as C
+
     from mmvae_amd import _lib
 
-    sizes = [(4099, 0, 5e-3, 1e-2), (1027, 1, 1e-3, 0.0)]
-    states = [_state(), _state(0.05)]
+    sizes = MULTI_SIZES
+    states = [_state(cv) for cv in MULTI_CV]
     hypers = [_hyper(lr, wd) for _, _, lr, wd in sizes]
-    results = []
-    for hp in (False, True):
-        arenas = [_arenas(n, off) for n, off, _, _ in sizes]
-        table = ((_lib.AdamArenaHp if hp else _lib.AdamArena) * len(sizes))()
-        for e, full, (n, off, lr, wd), st, hy in zip(table, arenas, sizes, states, hypers):
-            p, g, m, v = _views(full, n, off)
-            e.p, e.g, e.m, e.v, e.state, e.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), st.data_ptr(), n
-            e.beta1, e.beta2, e.eps, e.grad_scale = B1, B2, EPS, GS
-            if hp:
-                e.hyper = hy.data_ptr()
-            else:
-                e.lr, e.weight_decay = lr, wd
-        import ctypes as C
-
-        raw = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).cuda()
-        assert C.sizeof(table) == raw.numel()
-        fn = lib.mmvae_adam_step_multi_hp if hp else lib.mmvae_adam_step_multi
-        assert fn(len(sizes), raw.data_ptr(), max(n for n, _, _, _ in sizes), _stream()) == 0
-        torch.cuda.synchronize()
-        results.append(arenas)
-    for ref, got, (n, off, _, _) in zip(results[0], results[1], sizes):
-        for a, b in zip(ref, got):
-            assert torch.equal(a, b)
-        assert not torch.equal(got[0], _arenas(n, off)[0])
+    arenas = [_arenas(n, off) for n, off, _, _ in sizes]
+    table = (_lib.AdamArenaHp * len(sizes))()
+    for e, full, (n, off, lr, wd), st, hy in zip(table, arenas, sizes, states, hypers):
+        p, g, m, v = _views(full, n, off)
+        e.p, e.g, e.m, e.v, e.state, e.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), st.data_ptr(), n
+        e.beta1, e.beta2, e.eps, e.grad_scale = B1, B2, EPS, GS
+        e.hyper = hy.data_ptr()
+    raw = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).cuda()
+    assert C.sizeof(table) == raw.numel()
+    assert lib.mmvae_adam_step_multi_hp(len(sizes), raw.data_ptr(), max(n for n, _, _, _ in sizes), _stream()) == 0
+    torch.cuda.synchronize()
+    for k, (got, (n, off, _, _)) in enumerate(zip(arenas, sizes)):
+        fresh = _arenas(n, off)
+        p, g, m, v = _views(got, n, off)
+        for name, t in zip("pmv", (p, m, v)):
+            assert torch.equal(t, by_value[f"multi{k}_{name}"]), (k, name)
+        assert not torch.equal(got[0], fresh[0]) and torch.equal(got[1], fresh[1])
+        for t, f in zip(got, fresh):  # nothing written around the arena
+            assert torch.equal(t[:off], f[:off]) and torch.equal(t[off + n:], f[off + n:])
 
 
 def test_hp_entries_reject_bad_arguments(lib):

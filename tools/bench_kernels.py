@@ -61,8 +61,9 @@ def main():
     n = H1 * G * 2 + 2 * H1 * H2
     p, gr, m, v = r(n), r(n), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
     st, part = torch.zeros(8, device=dev), torch.empty(ops.sqnorm_partials(n), device=dev)
+    hyper = torch.tensor([5e-3, 1e-6, 0.0, 0.0], device=dev)  # lr, weight decay, coupled
     rec("k12 grad sqnorm", timeit(lambda: ops.clip_adam_step(p, gr, m, v, st, part, max_norm=10.0, do_step=False), a.iters), bytes_=4.0 * n)
-    rec("k13 adam step", timeit(lambda: ops.clip_adam_step(p, gr, m, v, st, part, do_norm=False), a.iters), bytes_=28.0 * n)
+    rec("k13 adam step", timeit(lambda: ops.clip_adam_step(p, gr, m, v, st, part, do_norm=False, hyper=hyper), a.iters), bytes_=28.0 * n)
     sl = r(16, B, H1)
     bn = dict(gamma=torch.ones(H1, device=dev), beta=torch.zeros(H1, device=dev), running_mean=torch.zeros(H1, device=dev),
               running_var=torch.ones(H1, device=dev), num_batches_tracked=None)

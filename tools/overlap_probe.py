@@ -24,6 +24,7 @@ W1 = torch.randn(H1, G, device=dev, generator=gen) * 0.01
 param, grad = torch.randn(P, device=dev, generator=gen), torch.randn(P, device=dev, generator=gen) * 1e-3
 m, v = torch.zeros(P, device=dev), torch.zeros(P, device=dev)
 state = torch.tensor([0, 0, 1, 1, 1, 0, 0, 0], dtype=torch.float32, device=dev)
+hyper = torch.tensor([5e-3, 0.0, 0.0, 0.0], device=dev)  # lr, weight decay, coupled
 main, side = torch.cuda.Stream(), torch.cuda.Stream()
 
 
@@ -32,8 +33,8 @@ def gemm():
 
 
 def adam():
-    rc = lib.mmvae_adam_step(P, param.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), state.data_ptr(), 5e-3,
-                             0.9, 0.999, 1e-8, 0.0, 1.0, torch.cuda.current_stream().cuda_stream)
+    rc = lib.mmvae_adam_step_hp(P, param.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), state.data_ptr(),
+                                hyper.data_ptr(), 0.9, 0.999, 1e-8, 1.0, torch.cuda.current_stream().cuda_stream)
     assert rc == 0
 
 
