@@ -75,8 +75,10 @@ def test_gemm_random(ops, layout, M, N, K, splitk):
 @pytest.mark.parametrize("layout", [0, 1, 2])
 @pytest.mark.parametrize("M,N,K", [(508, 19996, 72), (19996, 508, 72), (1024, 20000, 64), (20000, 1024, 40)])
 def test_gemm_wide_and_tall_tiles(ops, layout, M, N, K):
-    """Chip-filling outputs where the planner picks the 128x160 / 160x128 bf16x3 tiles (fewer rounds of resident
-    workgroups): ragged last tiles, a K tail (K % 32 != 0) and the DPP-transposed rows 128..159 of RC operands."""
+    """Chip-filling outputs with ragged last tiles.  With today's defaults (wave-specialised kernel on) the K = 64 cases
+    run its 256x160 / 160x256 tiles, and the cases with a K tail (K % 32 != 0: 72, 40) run the element-guarded 128x128
+    bf16x3 tile.  The 128x160 / 160x128 tiles of the 2 x 4-wave kernels, with the DPP-transposed rows 128..159 of
+    rows-contiguous operands, are reached with the family switch off: tests/test_gemm_launch_state_gpu.py."""
     a, b = _asym(M, K), _asym(K, N) + 1.0
     A = a if layout != 2 else a.t().contiguous()
     Bm = b.t().contiguous() if layout == 0 else b
@@ -103,7 +105,7 @@ def test_gemm_wave_specialised_kernel(ops, layout, M, N, K, monkeypatch):
 
     from mmvae_amd import _lib
 
-    monkeypatch.setenv("MMVAE_X3W", "1")  # (off by default: level with the 2 x 4-wave kernel inside the step)
+    monkeypatch.setenv("MMVAE_X3W", "1")  # (the default; pinned so that MMVAE_X3W=0 in the environment cannot reroute the test)
     t, sk = ctypes.c_int(), ctypes.c_int()
     a, b = rnd(M, K, seed=M + 7 * layout), rnd(K, N, seed=N + 3)
     ref = a.double() @ b.double()
