@@ -42,8 +42,10 @@ typedef void* mmvae_stream_t; /* hipStream_t */
  *   1  round-1 surface (first 20 entry points)      2  end of round 1 (50 entry points)      3+  round 2
  *   14 removed the Adam passes that took lr and weight decay by value -- mmvae_adam_step, mmvae_adam_step_copy,
  *      mmvae_adam_step_jobs, mmvae_adam_step_multi -- and the struct mmvae_adam_arena: their `_hp` forms of ABI 13 are the
- *      only Adam passes.  The names are not reused, so a caller of a retired symbol fails when it loads or binds. */
-#define MMVAE_ABI_VERSION 14
+ *      only Adam passes.  The names are not reused, so a caller of a retired symbol fails when it loads or binds.
+ *   15 added mmvae_col_pearson_f32 and mmvae_col_pearson_workspace_bytes (per-gene correlation of two generated
+ *      matrices, the statistic behind cross-generation). */
+#define MMVAE_ABI_VERSION 15
 int mmvae_abi_version(void);
 const char* mmvae_build_arch(void);
 
@@ -853,6 +855,30 @@ int mmvae_scale_rows(int B, int N, const float* x, int64_t ldx, const float* row
 int mmvae_weighted_colsum_chunks(int B);
 int mmvae_weighted_colsum_f32(int B, int N, const float* x, int64_t ldx, const float* row_weight, float* partials,
                               mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Per-gene Pearson correlation (ABI 15)
+ * replaces: the torch statement of the per-gene correlation between two generated expression matrices in the
+ * reference's runners (runners/cross_generation.py:87-152, runners/correlations.py:69-115: centre both [cells, genes]
+ * matrices, multiply, sum, divide -- several passes over 2 x cells x 60 530 floats), the statistic computed on what
+ * CMMVAE.forward(..., cross_generate=True) returns (modules/cmmvae.py:95-107).
+ *
+ *   r[g] = corr over the B rows of a[:, g] and b[:, g], clamped to [-1, 1]; NaN exactly when column g of a or of b is
+ *   constant (all-zero genes behind the output ReLU).  a == b is allowed.
+ *
+ * Each matrix is read ONCE.  Per column, five fp64 moments of the values shifted by the column's first row
+ * (da = a - a[0][g], db = b - b[0][g]: sum da, sum db, sum da^2, sum db^2, sum da db), then
+ * r = (n S_ab - S_a S_b) / sqrt((n S_aa - S_a^2)(n S_bb - S_b^2)) in fp64, stored as fp32.  The shift makes a constant
+ * column's moments exact zeros and removes the mean^2 / variance cancellation (fp32 raw moments are off by 1e-2 at
+ * mean 100, sigma 1).  Row chunks leave fp64 partials in `workspace` (mmvae_col_pearson_workspace_bytes(B, G) bytes,
+ * 8-byte aligned), which a second small launch of the same call adds in chunk order: fixed summation order, no
+ * atomics, bitwise reproducible.  16-byte loads when both base pointers are 16-byte aligned and both leading
+ * dimensions multiples of 4, element-wise otherwise.  B < 2, G < 1, a null pointer, a leading dimension below G or a
+ * workspace that is too small: MMVAE_ERR_ARG, nothing is launched.
+ * ------------------------------------------------------------------------------------------------------------ */
+size_t mmvae_col_pearson_workspace_bytes(int B, int G);
+int mmvae_col_pearson_f32(int B, int G, const float* a, int64_t lda, const float* b, int64_t ldb, float* r /* [G] */,
+                          void* workspace, size_t workspace_bytes, mmvae_stream_t stream);
 
 #ifdef __cplusplus
 }

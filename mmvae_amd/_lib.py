@@ -170,6 +170,8 @@ PROTOTYPES = {
     "mmvae_adam_step_multi_hp": (_i, [_i, _p, _l, _p]),
     "mmvae_ell_from_dense_f32": (_i, [_i, _i, _p, _l, _i, _p, _p, _p, _p]),
     "mmvae_dw_sparse_ell_f32": (_i, [_i, _i, _i, _p, _l, _p, _p, _p, _i, _p, _l, _p]),
+    "mmvae_col_pearson_workspace_bytes": (_z, [_i, _i]),
+    "mmvae_col_pearson_f32": (_i, [_i, _i, _p, _l, _p, _l, _p, _p, _z, _p]),
 }
 
 

@@ -33,7 +33,7 @@ import torch
 from . import _lib, dist as mdist, rng
 from .constants import REGISTRY_KEYS as RK
 from .engine_adv import PlanAdversaries
-from .engine_common import ACC, NN, NT, SQ_FUSED_SLOTS, TN, _LayerRef, _PlaneBuf, _block_decline, _p
+from .engine_common import ACC, NN, NT, RELU, SQ_FUSED_SLOTS, TN, _LayerRef, _PlaneBuf, _block_decline, _p
 from .engine_cond import CondProgram
 from .engine_emit import PlanEmit
 from .engine_run import PlanRun
@@ -191,9 +191,11 @@ def plan_layout(st: EngineSettings, *, fork_ok: bool, side_stream: bool, side_st
 
 
 # Plan keys.  Training programs: (mode, expert, B, K, explicit, slabs ahead, target, pointer, stride); forward-only ones the
-# same without "slabs ahead" and "target".  pointer / stride: the current batch read in place, (0, 0) = through the
-# expert's static input buffer.  target: None, or (expert, pointer, shape, stride) of the announced batch the program
-# computes ahead for; pointer 0 = through that expert's static input buffer.
+# same without "slabs ahead" and "target"; a "generate" program carries the tuple of its target experts behind
+# "explicit".  pointer / stride: the current batch read in place, (0, 0) = through the expert's static input buffer --
+# always the key's last two elements, which is where _key_pointer looks: the extra element of generate keys moves nothing
+# it reads.  target: None, or (expert, pointer, shape, stride) of the announced batch the program computes ahead for;
+# pointer 0 = through that expert's static input buffer.
 def _key_pointer(key: tuple) -> int:
     """The caller's pointer a plan reads its batch from, 0 when it reads the static input buffer."""
     return key[-2]
@@ -340,6 +342,7 @@ class StepEngine:
         self.prefetch_stats = {"issued": 0, "consumed": 0, "discarded": 0, "staged_ahead": 0}
         self._next_seen: Dict[tuple, int] = {}   # announced batches by (expert, pointer, stride, shape): resident or streamed?
         self._staged: Optional[tuple] = None     # (expert, tensor, signature) of the batch staged ahead into x_static.<expert>
+        self.last_forward_key: Optional[tuple] = None  # introspection: the key of the forward-only program that ran last
 
     def _configure_parallel(self) -> None:
         """Overlapped data parallelism (default whenever gradients are exchanged).  The active expert's parameters are
@@ -691,9 +694,10 @@ class StepEngine:
             opt.sync_hyper()
 
     # ------------------------------------------------------------------------------------- eval / predict (f3)
-    def _forward_only(self, mode: str, x: torch.Tensor, expert_id: str, metadata=None):
+    def _forward_only(self, mode: str, x: torch.Tensor, expert_id: str, metadata=None, targets: tuple = ()):
         """Forward-only plan (no autograd, no gradients, no optimiser): eval-mode BatchNorm (running statistics), no
-        dropout, one rsample.  mode "validate": + fused reconstruction / ELBO; mode "embed": stops at z."""
+        dropout, one rsample.  mode "validate": + fused reconstruction / ELBO; mode "embed": stops at z; mode "generate":
+        + the shared decoder once and the decoder of every expert in `targets` (part of the plan key)."""
         x = self._dense_f32(x)
         ev = self._pending.pop(expert_id, None)
         if ev is not None:
@@ -704,16 +708,18 @@ class StepEngine:
         # (forward-only programs read the batch through the K-contiguous forward GEMM and the reconstruction epilogue's
         # guarded loads only: any caller's tensor serves as it is)
         self._drop_lookahead()  # (the static input buffers are rewritten; a training step behind this one starts afresh)
-        key, x_in, _ = self._select_input(x, (mode, expert_id, B, 1, explicit), needs_slack=False)
+        key, x_in, _ = self._select_input(x, (mode, expert_id, B, 1, explicit) + ((targets,) if targets else ()),
+                                          needs_slack=False)
         plan = self._plans.get(key)
         if plan is None:
-            plan = _Plan(self, expert_id, B, 1, explicit, x_in, mode=mode)
+            plan = _Plan(self, expert_id, B, 1, explicit, x_in, mode=mode, targets=targets)
             self._plans[key] = plan
         self._set_kl_weight()
         if explicit:
             plan.eps.copy_(enc_mod.explicit_eps.reshape(plan.eps.shape))
         if plan.cond is not None:
             plan.cond.load(metadata)
+        self.last_forward_key = key  # introspection (tests: which program the call ran)
         plan.run()
         if plan.cond is not None:
             plan.cond.commit()
@@ -730,6 +736,42 @@ class StepEngine:
         """z of `CMMVAE.get_latent_embeddings` (modules/cmmvae.py:115-142) as one captured forward program."""
         plan = self._forward_only("embed", x, expert_id)
         return plan.z[0].clone()
+
+    def cross_generate(self, x: torch.Tensor, metadata, expert_id: str, targets=None, decode_metadata=None,
+                       copy: bool = True):
+        """Cross-generation (`CMMVAE.forward(..., cross_generate=True)`, modules/cmmvae.py:95-107) as one captured forward
+        program: the encoder of `expert_id`, the heads and z, the conditional layers, the shared decoder ONCE, then the
+        decoder of every target expert.  Returns (z, {target: xhat [B, genes of the target]}); z is the one
+        `CMMVAE.forward` returns: the latent sample [B, Z], with conditional layers what THEY make of it under
+        `decode_metadata` ([B, Z], or [B, positions x Z] for the "parallel" selection order).
+        targets: None = every expert in `module.experts` order; one id, or any ordered subset (KeyError for an unknown
+        id).  One program is built per (source, targets, B, input pointer class).
+        decode_metadata: what the conditional layers are loaded with (default: `metadata`) -- the source cells' z decoded
+        under edited metadata, the reference's counterfactual generation (runners/cross_generation.py:131-152); ignored
+        by models without conditional layers, ValueError when it has not B rows.
+        copy=True returns clones; copy=False returns views of the engine's own buffers (each xhat a `[:, :G]` view of a
+        buffer whose leading dimension is G rounded up to 4), which stay valid until the next call into the engine."""
+        experts = self.model.module.experts
+        if targets is None:
+            targets = tuple(experts.keys())
+        elif isinstance(targets, str):
+            targets = (targets,)
+        else:
+            targets = tuple(targets)
+        for t in targets:
+            if t not in experts:
+                raise KeyError(f"cross_generate: {t!r} is not an expert of this model ({list(experts.keys())})")
+        if not targets:
+            raise ValueError("cross_generate: no target expert")
+        if decode_metadata is None:
+            decode_metadata = metadata
+        if getattr(self.model.module.vae, "conditionals", None) is not None and len(decode_metadata) != x.shape[0]:
+            raise ValueError(f"cross_generate: decode_metadata has {len(decode_metadata)} rows, the batch {x.shape[0]}")
+        plan = self._forward_only("generate", x, expert_id, decode_metadata, targets=targets)
+        z, xhats = plan.z_out, dict(plan.xhat)
+        if copy:
+            z, xhats = z.clone(), {t: v.clone() for t, v in xhats.items()}
+        return z, xhats
 
     # --------------------------------------------------------------------------------------------------- step
     # ------------------------------------------------------------------- software pipelining across steps (r5)
@@ -882,9 +924,11 @@ class StepEngine:
 
 class _Plan(PlanEmit, PlanAdversaries, PlanRun):
     def __init__(self, eng: StepEngine, eid: str, B: int, K: int, explicit: bool, x: torch.Tensor, mode: str = "train",
-                 iwae: bool = False, slabs_ahead: Optional[torch.Tensor] = None, prefetch=None):
+                 iwae: bool = False, slabs_ahead: Optional[torch.Tensor] = None, prefetch=None, targets: tuple = ()):
         self.eng, self.eid, self.B, self.K, self.explicit = eng, eid, B, K, explicit
         self.mode = mode
+        self.targets = tuple(targets)     # "generate" programs: the experts whose decoders run, in order
+        self.xhat: Dict[str, torch.Tensor] = {}  # ... and what they leave: target -> [R, G] view of an engine buffer
         # software pipelining across steps (StepEngine.training_step): slabs of this step's first forward product that
         # the previous step computed, and the (expert id, batch) this step computes them for
         self.slabs_ahead, self.prefetch, self.prefetch_slabs = slabs_ahead, prefetch, None
@@ -897,9 +941,7 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
         g = eng.grad_of
         exp = m.experts[eid]
 
-        def refs(block: FCBlock):
-            return [_LayerRef(seq, g, block.config.return_hidden[i], block, i) for i, seq in enumerate(block.fc_layers)]
-
+        refs = self._layer_refs
         self.enc_layers = refs(exp.encoder) + refs(m.vae.encoder.fc)
         self.n_expert_enc = len(exp.encoder.fc_layers)
         self.dec_layers = refs(m.vae.decoder) + refs(exp.decoder)
@@ -980,6 +1022,11 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
             adv_reducer=any(o.reducer is not None for o in self.opt_adv))
         self._build()
 
+    def _layer_refs(self, block: FCBlock) -> list:
+        """The layers of an FCBlock bound to their parameters and gradient-arena views."""
+        g = self.eng.grad_of
+        return [_LayerRef(seq, g, block.config.return_hidden[i], block, i) for i, seq in enumerate(block.fc_layers)]
+
     # ------------------------------------------------------------------------------------------- program building
     def _build(self):
         """Emit the step's program, phase by phase (branch streams as self.layout places them)."""
@@ -989,6 +1036,9 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
         self._emit_encoder_forward()
         self._emit_heads()
         if self.mode == "embed":  # predict path: the program ends at z
+            return self._finish_forward_only()
+        if self.mode == "generate":  # cross-generation: the program ends with every target's xhat
+            self._emit_generate()
             return self._finish_forward_only()
         adv = self._emit_adversaries()
         loss_calls = self._emit_decoder_forward()
@@ -1242,6 +1292,40 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
         # K = 1: the backward pass starts from dP, which the reconstruction epilogue has already written; the loss words
         # are only logged -- their two launches leave the critical path
         return self._take(start) if (L.early and not self.has_adv) else []
+
+    def _emit_generate(self):
+        """Cross-generation: the conditional layers, the shared VAE decoder once, then every target expert's decoder on
+        its output.  A target's last layer is a plain Linear + ReLU product (bias and ReLU in the GEMM's epilogue) into
+        an engine-owned xhat buffer -- no x of the target's gene count exists for the fused reconstruction launch.  The
+        buffers' leading dimension is the gene count rounded up to 4 (60 530 / 52 437 are no multiples of 4): rows stay
+        16-byte regular for whatever reads them next (mmvae_col_pearson_f32)."""
+        eng = self.eng
+        m = eng.model.module
+        R, Z = self.R, self.Z
+        cur, ld = self.z, Z
+        if self.cond is not None:  # CLVAE.after_reparameterize
+            cur, ld = self.cond.emit_forward(self.z)
+        self.z_out = cur if self.cond is not None else self.z[0]  # the z CMMVAE.forward returns: behind the conditional layers
+
+        n_shared = len(m.vae.decoder.fc_layers)  # (dec_layers: the shared decoder's layers, then the source expert's)
+        for i, l in enumerate(self.dec_layers[:n_shared]):
+            cur = self.fwd_layer(f"gen.vae.dec{i}", l, cur, ld, R, training=False)
+            ld = l.n_out
+        for t in self.targets:
+            t_cur, t_ld = cur, ld
+            layers = self.dec_layers[n_shared:] if t == self.eid else self._layer_refs(m.experts[t].decoder)
+            for i, l in enumerate(layers[:-1]):
+                t_cur = self.fwd_layer(f"gen.{t}.dec{i}", l, t_cur, t_ld, R, training=False)
+                t_ld = l.n_out
+            last = layers[-1]
+            if not (last.relu and last.bn is None and last.ln is None and last.p == 0):
+                raise _lib.HipLibraryError("engine: the last decoder layer must be Linear+ReLU (fused recon epilogue)")
+            G = last.n_out
+            ldx = (G + 3) // 4 * 4
+            out = eng.buf(f"xhat.{t}", (R, ldx))
+            self.gemm(NT, R, G, last.n_in, t_cur, t_ld, last.W, last.n_in, out, ldx, bias=last.b, flags=RELU)
+            self.xhat[t] = out[:, :G]
+        self._mark("generated")
 
     def _emit_adversaries_inline(self, adv):
         """Total loss = ELBO loss + adv_weight * sum of the generator-phase losses (cmmvae_model.py:182-184; without

@@ -258,3 +258,18 @@ def fc_layer(x, weight, bias, *, gamma=None, beta=None, bn_state: Optional[dict]
     """Returns (d, a): layer output and post-activation / pre-dropout tensor (the same object without dropout)."""
     out = FCLayerFn.apply(x, weight, bias, gamma, beta, bn_state, training, relu, keep_mask, dropout_p)
     return out if isinstance(out, tuple) else (out, out)
+
+
+def col_pearson(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Per-gene Pearson correlation r [G] of two [cells, genes] matrices, NaN where a column of either is constant --
+    the statistic of runners/cross_generation.py:87-152 and runners/correlations.py:69-115.  Device tensors: one
+    read-once HIP launch (ops.col_pearson).  CPU tensors only under backend.cpu_plumbing(): the centred two-pass
+    statement in fp64 (host-logic tests)."""
+    from . import backend
+
+    if backend.on_hip(a):
+        return ops.col_pearson(a, b)
+    da, db = a.double() - a.double().mean(0), b.double() - b.double().mean(0)
+    r = (da * db).sum(0) / torch.sqrt((da * da).sum(0) * (db * db).sum(0))
+    constant = (a == a[0]).all(0) | (b == b[0]).all(0)
+    return torch.where(constant, torch.full_like(r, float("nan")), r.clamp(-1.0, 1.0)).float()

@@ -273,6 +273,56 @@ class CMMVAEModel(BaseModel):
             return {RK.Z: (z, metadata)}
         return self.module.get_latent_embeddings(x, metadata, species)
 
+    @torch.no_grad()
+    def cross_generate_step(self, batch, batch_idx: int = 0, targets=None, decode_metadata=None):
+        """Cross-generation (`CMMVAE.forward(..., cross_generate=True)`, modules/cmmvae.py:95-107; the loop of
+        runners/cross_generation.py:87-152): encode the batch with its own expert, decode the one latent sample through
+        every expert in `targets` (None: all of them, in `module.experts` order; one id or an ordered subset otherwise).
+        `decode_metadata` (default: the batch's metadata) is what the conditional layers see: the cells' z decoded under
+        edited metadata, the reference's counterfactual generation (:131-152); it must have one row per cell.
+        Returns {"z": (z, metadata), "xhat_<target>": (xhat, metadata), ...} -- the {key: (data, metadata)} shape
+        PredictionWriter appends to predictions.h5; z is the one `CMMVAE.forward` returns (behind the conditional layers,
+        under `decode_metadata`, when the model has them; predict_step gives the latent sample in front of them).  metadata["species"] = expert_id is written in place, as predict_step
+        does.  In eval mode on the device this is one captured engine program (StepEngine.cross_generate); in training
+        mode (with the reference's warning), on CPU plumbing and for models the engine declines it is the module path."""
+        self._flush_engine()
+        x, metadata, expert_id = batch
+        module = self.module
+        names = list(module.experts.keys()) if targets is None else ([targets] if isinstance(targets, str) else list(targets))
+        for name in names:
+            if name not in module.experts:
+                raise KeyError(f"cross_generate_step: {name!r} is not an expert of this model ({list(module.experts.keys())})")
+        decode_md = metadata if decode_metadata is None else decode_metadata
+        if getattr(module.vae, "conditionals", None) is not None and len(decode_md) != x.shape[0]:
+            raise ValueError(f"cross_generate_step: decode_metadata has {len(decode_md)} rows, the batch {x.shape[0]}")
+        engine = None if module.training else self._get_engine(x)
+        if engine is not None:
+            z, xhats = engine.cross_generate(x, metadata, expert_id, targets=names, decode_metadata=decode_md)
+        else:
+            if module.training:
+                import warnings
+
+                warnings.warn("CMMVAE is cross-generating during training: gradients accumulate for every expert")
+            _, z, _ = module.vae.encode(module.experts[expert_id].encode(x))
+            z = module.vae.after_reparameterize(z, decode_md, species=expert_id)  # (the z CMMVAE.forward returns)
+            shared = module.vae.decode(z)
+            xhats = {name: module.experts[name].decode(shared) for name in names}
+        metadata["species"] = expert_id
+        out = {RK.Z: (z, metadata)}
+        out.update({f"xhat_{name}": (xhat, metadata) for name, xhat in xhats.items()})
+        return out
+
+    @staticmethod
+    def gene_correlation(a: torch.Tensor, b: torch.Tensor):
+        """(r, mean_r, n_valid) of two [cells, genes] matrices, e.g. two entries of cross_generate_step or a generated
+        matrix against the measured one: r [genes] the per-gene Pearson correlation (HF.col_pearson: one HIP launch on
+        device tensors), NaN where a gene is constant in either matrix; mean_r the mean over the genes that have one
+        (torch.nanmean); n_valid their count.  The reference takes a plain `.mean()` over r
+        (runners/correlations.py:69-115), which is NaN as soon as ONE gene is dead -- all-zero genes behind the output
+        ReLU are the common case -- so mean_r differs from it exactly where the reference's value is NaN."""
+        r = HF.col_pearson(a, b)
+        return r, torch.nanmean(r), (~torch.isnan(r)).sum()
+
     # -------------------------------------------------------------------------------------------------- optimisers
     def get_optimizers(self, zero_all: bool = False):
         """The optimisers in the shape of `optimizer_map`: {"experts": {id: opt}, "vae": opt, "adversarials": {n: opt}}

@@ -939,3 +939,27 @@ def scale_rows(x: torch.Tensor, row_scale: torch.Tensor, out: Optional[torch.Ten
     _lib.check(lib.mmvae_scale_rows(B, N, _ptr(x), ldx, _ptr(row_scale), _ptr(out), _mat(out, "out")[2], _stream()),
                "mmvae_scale_rows")
     return out
+
+
+def col_pearson(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """r [G]: the Pearson correlation over the rows of column g of `a` and of `b` (mmvae_col_pearson_f32: each matrix
+    read once, fp64 moments of the values shifted by the first row, fixed summation order), clamped to [-1, 1]; NaN
+    exactly where a column of `a` or of `b` is constant.  `a` and `b`: [B, G] fp32 with B >= 2, row-major views with any
+    row stride (a `[:, :G]` view of a wider buffer serves as it is); `a is b` is allowed."""
+    lib = _lib.load()
+    _chk(a, "a"), _chk(b, "b"), _chk(out, "out")
+    B, G, lda = _mat(a, "a")
+    Bb, Gb, ldb = _mat(b, "b")
+    if (Bb, Gb) != (B, G):
+        raise ValueError(f"col_pearson: a {tuple(a.shape)} vs b {tuple(b.shape)}")
+    if b.device != a.device or (out is not None and out.device != a.device):
+        raise ValueError(f"col_pearson: a, b and out must be on one device (a on {a.device}, b on {b.device})")
+    if out is None:
+        out = torch.empty((G,), dtype=torch.float32, device=a.device)
+    elif out.shape != (G,) or not out.is_contiguous():
+        raise ValueError(f"col_pearson: out must be a contiguous [{G}] tensor")
+    nbytes = lib.mmvae_col_pearson_workspace_bytes(B, G)
+    ws = workspace(nbytes, a.device, kind="col_pearson")
+    _lib.check(lib.mmvae_col_pearson_f32(B, G, _ptr(a), lda, _ptr(b), ldb, _ptr(out), _ptr(ws), nbytes, _stream()),
+               "mmvae_col_pearson_f32")
+    return out

@@ -149,3 +149,17 @@ class Trainer:
             writer.write_on_batch_end(self, model, model.predict_step(batch, i), None, batch, i, 0)
         writer.on_predict_epoch_end(self, model)
         return []
+
+    @torch.no_grad()
+    def cross_generate(self, model, batches: Iterable, targets=None, writer=None) -> list:
+        """`cross_generate_step` over the batches, like predict(): eval mode, stage "prediction"; with a
+        PredictionWriter every batch's z and xhat_<target> matrices are appended to predictions.h5 and nothing is kept."""
+        model.eval()
+        model.trainer.set_stage("prediction")
+        if writer is None:
+            return [model.cross_generate_step(batch, i, targets=targets) for i, batch in enumerate(batches)]
+        writer.on_predict_start(self, model)
+        for i, batch in enumerate(batches):
+            writer.write_on_batch_end(self, model, model.cross_generate_step(batch, i, targets=targets), None, batch, i, 0)
+        writer.on_predict_epoch_end(self, model)
+        return []
