@@ -887,6 +887,10 @@ __device__ __forceinline__ u32x4 philox4x32_10(uint64_t counter, uint64_t stream
     }
     return {c0, c1, c2, c3};
 }
+// Uniform in [2^-25, 1.0] from the top 24 bits k of a word: (k + 0.5) 2^-24.  k + 0.5f is not representable from
+// k = 2^23 on and rounds to even, so k = 2^24 - 1 gives exactly 1.0f (k = 2^23 gives exactly 0.5f).  Both ends are safe:
+// the value is never 0, so logf stays finite (the largest radius is sqrt(50 ln 2) = 5.89); u0 == 1.0f gives radius -0 and
+// a pair of exact zeros; a keep mask compares u >= p_drop with p_drop < 1, so u == 1.0f keeps like its neighbours.
 __device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
 __global__ __launch_bounds__(256) void philox_mask_kernel(int64_t n, float p_drop, uint8_t* __restrict__ mask,
