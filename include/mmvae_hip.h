@@ -44,8 +44,12 @@ typedef void* mmvae_stream_t; /* hipStream_t */
  *      mmvae_adam_step_jobs, mmvae_adam_step_multi -- and the struct mmvae_adam_arena: their `_hp` forms of ABI 13 are the
  *      only Adam passes.  The names are not reused, so a caller of a retired symbol fails when it loads or binds.
  *   15 added mmvae_col_pearson_f32 and mmvae_col_pearson_workspace_bytes (per-gene correlation of two generated
- *      matrices, the statistic behind cross-generation). */
-#define MMVAE_ABI_VERSION 15
+ *      matrices, the statistic behind cross-generation).
+ *   16 one entry point per launch family: mmvae_decoder_recon (struct mmvae_recon_args) replaces the five positional
+ *      reconstruction entries and the process-wide k-padding switch (now the per-call flag MMVAE_RECON_H_KPAD);
+ *      mmvae_fc_epilogue_fwd / _bwd take their optional planes and split job as nullable struct pointers; the unsplit
+ *      GEMM with norm partials is mmvae_gemm_planes_f32 alone.  The retired names are not reused. */
+#define MMVAE_ABI_VERSION 16
 int mmvae_abi_version(void);
 const char* mmvae_build_arch(void);
 
@@ -122,31 +126,57 @@ int mmvae_gemm_f32(int layout, int M, int N, int K, float alpha, const float* A,
  *
  * The per-cell squared error is reduced across the wavefront with shuffles inside the GEMM epilogue; the
  * [tiles, B] partials are summed in fixed order by mmvae_elbo_finalize (bitwise reproducible, no atomics).
+ *
+ * One entry point, its arguments in a struct that is read on the host during the call only (the caller may free it on
+ * return).  Optional members are NULL when absent:
+ *   rows, x_rows  K-sample form: `rows` = K*B stacked decoder inputs, x has x_rows = B rows (K = 1: rows == x_rows),
+ *                 output row r compares with x[r % B]; se_part is [tiles, rows].
+ *   col_part      also leaves the column sums of dP (= the gradient of the layer's bias when the rows are not re-weighted
+ *                 afterwards, K = 1) as per-row-tile partials [mmvae_recon_row_tiles(rows)][G], to be summed over the row
+ *                 tiles in order (mmvae_sum_parts_batch).  Saves the separate pass over the [rows, G] gradient (41 MB at
+ *                 C2).  Replaces: autograd of `bias` in components.py:276.
+ *   dP_planes     the epilogue also writes the three bf16 planes of dP (G % 8 == 0, bf16x3 precision; dP itself may then
+ *                 be NULL): the weight-gradient and input-gradient GEMMs that consume dP read it pre-split (see
+ *                 "Pre-split operands" below for the plane layout).
+ *   h_planes      the decoder's hidden activations h pre-split (h may then be NULL): runs the wave-specialised kernel
+ *                 (256-row tiles; col_part keeps its layout, one partial per 128-row half) when the shape fills the chip,
+ *                 otherwise falls back to the fp32 h if given.  (Measured slower than the two-workgroup kernel on fp32 h
+ *                 at C2: its epilogue is done by 4 of the 8 waves; kept for shapes where the main loop dominates.)
+ *   W_planes      (r5) the WEIGHTS pre-split as well ([G][ld] planes of W; taken together with h_planes -- without
+ *                 h_planes, or where h_planes cannot be used, W is read as fp32).  A K-sample program reads every weight
+ *                 tile from rows / 256 row tiles (20 at BASELINE config 3) and splits it there each time; with both
+ *                 operands pre-split the stagers only move planes (LDS-DMA, no vector work).  The caller re-splits W
+ *                 after every optimiser step (mmvae_split_planes_f32, or the piggy-backed split of a layer tail).
+ *                 W_planes together with dP_planes is refused with MMVAE_ERR_ARG: no kernel was ever launched with both.
+ *   flags         MMVAE_RECON_H_KPAD: the caller vouches, for THIS call's buffers, that h has ZERO columns from H up to
+ *                 the next multiple of 32 inside its leading dimension and that every row of W may be read that far (the
+ *                 next row; 32 readable floats behind the last one).  A hidden width that is not a multiple of the
+ *                 32-wide k-tile (e.g. 1000) then takes the pipelined kernels over the padded K instead of the guarded
+ *                 loop (2 x slower).  Results: the products beyond H are exact zeros.  Ignored with h_planes.  Any other
+ *                 bit: MMVAE_ERR_ARG.
+ * With planes: the same products in the same order as the fp32 form, bit-identical outputs.
  * ------------------------------------------------------------------------------------------------------------ */
+typedef struct mmvae_planes { /* three bf16 planes of a matrix (layout: "Pre-split operands" below); p == NULL: absent */
+    uint16_t* p;
+    int64_t ld, plane_stride; /* bf16 elements */
+} mmvae_planes;
+#define MMVAE_RECON_H_KPAD 1u
+typedef struct mmvae_recon_args {
+    int32_t rows, x_rows, G, H;
+    uint32_t flags, reserved; /* MMVAE_RECON_H_KPAD; reserved = 0 */
+    const float *h, *W, *bias, *x;
+    int64_t ldh, ldw, ldx;
+    float *xhat, *dP, *se_part, *col_part;
+    int64_t ldxhat, lddp;
+    mmvae_planes h_planes, W_planes, dP_planes;
+} mmvae_recon_args;
 int mmvae_recon_tiles(int G);
-int mmvae_decoder_recon_f32(int B, int G, int H, const float* h, int64_t ldh, const float* W, int64_t ldw,
-                            const float* bias, const float* x, int64_t ldx, float* xhat, int64_t ldxhat, float* dP,
-                            int64_t lddp, float* se_part, mmvae_stream_t stream);
-/* K-sample form: `rows` = K*B stacked decoder inputs, x has x_rows = B rows, output row r compares with x[r % B];
- * se_part is [tiles, rows]. */
-int mmvae_decoder_recon_rows_f32(int rows, int x_rows, int G, int H, const float* h, int64_t ldh, const float* W,
-                                 int64_t ldw, const float* bias, const float* x, int64_t ldx, float* xhat,
-                                 int64_t ldxhat, float* dP, int64_t lddp, float* se_part, mmvae_stream_t stream);
-/* Launch state for the fused decoder / reconstruction entry points (host side, read when a launch is enqueued): on = the
- * caller vouches that h has ZERO columns from H up to the next multiple of 32 inside its leading dimension and that
- * every row of W may be read that far (the next row; 32 readable floats behind the last one).  A hidden width that is
- * not a multiple of the 32-wide k-tile (e.g. 1000) then takes the pipelined kernels over the padded K instead of the
- * guarded loop (2 x slower).  Results: the products beyond H are exact zeros. */
-int mmvae_recon_set_h_kpad(int on);
-/* The same launch, also leaving the column sums of dP (= the gradient of the layer's bias when the rows are not
- * re-weighted afterwards, K = 1) as per-row-tile partials: col_part [mmvae_recon_row_tiles(rows)][G], to be summed over
- * the row tiles in order (mmvae_sum_parts_batch).  col_part = NULL: exactly mmvae_decoder_recon_rows_f32.  Saves the
- * separate pass over the [rows, G] gradient (41 MB at C2).  Replaces: autograd of `bias` in components.py:276. */
 int mmvae_recon_row_tiles(int rows);
-int mmvae_decoder_recon_rows_colsum_f32(int rows, int x_rows, int G, int H, const float* h, int64_t ldh, const float* W,
-                                        int64_t ldw, const float* bias, const float* x, int64_t ldx, float* xhat,
-                                        int64_t ldxhat, float* dP, int64_t lddp, float* se_part, float* col_part,
-                                        mmvae_stream_t stream);
+int mmvae_decoder_recon(const mmvae_recon_args* args, mmvae_stream_t stream);
+/* sizeof of the argument structs as this library was compiled: what a binding checks its mirror of them against */
+size_t mmvae_sizeof_planes(void);
+size_t mmvae_sizeof_recon_args(void);
+size_t mmvae_sizeof_split_job(void);
 
 /* ------------------------------------------------------------------------------------------------------------
  * FCBlock layer epilogues ("column kernels")
@@ -160,6 +190,14 @@ int mmvae_decoder_recon_rows_colsum_f32(int rows, int x_rows, int G, int H, cons
  *            d = mask ? a * mask * (1 / (1 - p)) : a        (mask: u8 0/1 keep mask, parity mode or Philox-filled)
  * Outputs: z_out (needed by BN backward; may be NULL when !has_bn), a_out (may be NULL when no dropout and
  *          d_out given), d_out, save_mean / save_invstd [N] (training BN only).
+ * Optional, NULL when absent (structs read on the host during the call only):
+ *   d_planes  also write the three bf16 planes of d_out (N even): the layer tails that produce an operand of a G-wide
+ *             weight-gradient GEMM (the decoder's last hidden activations) split it on the way out.
+ *   split     a piggy-backed pass: extra workgroups of the second launch split the unrelated fp32 matrix
+ *             split->src [rows, cols] into its bf16 planes split->planes (as mmvae_split_planes_f32; planes.p == NULL:
+ *             MMVAE_ERR_ARG).  The engine splits its input batch this way beside the first layer's tail: as a launch of
+ *             its own the pass sits on the critical path of the step.
+ *   d_planes together with split is refused with MMVAE_ERR_ARG: no kernel was ever launched with both.
  * ------------------------------------------------------------------------------------------------------------ */
 typedef struct mmvae_bn_params {
     const float* gamma;        /* [N] bn.weight */
@@ -175,11 +213,19 @@ typedef struct mmvae_bn_params {
  * any backward that produces dbias / BN gradients). */
 size_t mmvae_fc_workspace_bytes(int B, int N);
 
+typedef struct mmvae_split_job {
+    int32_t rows, cols;
+    const float* src;
+    int64_t ld_src;
+    mmvae_planes planes;
+} mmvae_split_job;
+
 int mmvae_fc_epilogue_fwd(int B, int N, const float* in, int64_t ld_in, int n_slabs, const float* bias,
                           const mmvae_bn_params* bn /* NULL = no BN */, int training, int relu,
                           const uint8_t* keep_mask /* [B,N] or NULL */, float dropout_p, float* z_out,
                           float* a_out, float* d_out, int64_t ld_out, float* save_mean, float* save_invstd,
-                          float* workspace, size_t workspace_bytes, mmvae_stream_t stream);
+                          float* workspace, size_t workspace_bytes, const mmvae_planes* d_planes /* or NULL */,
+                          const mmvae_split_job* split /* or NULL */, mmvae_stream_t stream);
 
 /* Backward of the same layer tail.
  *   dd   = row_scale[b] * (sum_s din[s] + addend)        (grad wrt d; addend/row_scale optional)
@@ -194,13 +240,15 @@ int mmvae_fc_epilogue_fwd(int B, int N, const float* in, int64_t ld_in, int n_sl
  * dz_out may be NULL (pure column sum).  dz_out may alias din when n_slabs == 1.
  * Without BN, a non-NULL workspace always receives the per-row-chunk column partials of dz as [ceil(B/32)][N] floats;
  * they are summed into dbias when dbias is non-NULL.  With dbias == NULL the caller finishes them itself, e.g.
- * together with other pending reductions in one mmvae_sum_parts_batch launch. */
+ * together with other pending reductions in one mmvae_sum_parts_batch launch.
+ * dz_planes (or NULL): also write the three bf16 planes of the final dz_out (N even) -- the gradient at the expert
+ * encoder's first layer, an operand of a G-wide weight-gradient GEMM, is split on the way out. */
 int mmvae_fc_epilogue_bwd(int B, int N, const float* din, int64_t ld_in, int n_slabs, const float* addend,
                           const float* addend_a, const float* row_scale, const uint8_t* keep_mask, float dropout_p, int relu,
                           const float* a, const float* z, const float* gamma, const float* save_mean,
                           const float* save_invstd, int has_bn, float* dz_out, int64_t ld_out, float* dbias,
                           float* dgamma, float* dbeta, float* workspace, size_t workspace_bytes,
-                          mmvae_stream_t stream);
+                          const mmvae_planes* dz_planes /* or NULL */, mmvae_stream_t stream);
 
 /* LayerNorm(elementwise_affine=False), eps 1e-5 (components.py:281) -- used by ConditionalLayer blocks ("next" row f2). */
 int mmvae_layernorm_fwd(int B, int N, const float* x, int64_t ldx, float eps, float* y, int64_t ldy, float* save_mean,
@@ -273,7 +321,7 @@ int mmvae_mse_sum_fwd_bwd(int B, int G, const float* xhat, int64_t ldxhat, const
  * ELBO finalisation (a6) and the K-sample extension (a7 / k10)
  * replaces: vae.py:136-152 (loss = recon + kl_weight * mean_b KL_b).  K > 1 is a build-defined extension
  * (SURVEY 0): recon = sum_b -logmeanexp_k(-SE[b,k]); K = 1 reduces exactly to the reference.
- *   se_part: [T, K*B] partial squared errors (T = tiles of mmvae_decoder_recon_f32, or 1 for mse_sum rows),
+ *   se_part: [T, K*B] partial squared errors (T = tiles of mmvae_decoder_recon, or 1 for mse_sum rows),
  *            sample k of cell b at column k*B + b.
  *   out[0] = loss, out[1] = recon, out[2] = kl (mean over cells), out[3] = kl_weight, out[4] = mean(mu),
  *   out[5] = mean(var)      (accumulated in fp64, stored fp32)
@@ -363,7 +411,7 @@ int mmvae_adam_get_workgroups(void);
 /* The norm pass over 1..4 ranges of a gradient arena (e.g. what no fused GEMM epilogue covers) AND mmvae_adam_prepare
  * in one launch: range i = grads[i][0 .. lens[i]); its mmvae_sqnorm_partials(lens[i]) partials are written behind each
  * other at `partials`; the workgroup that finishes last (`ticket`: one zero-initialised word the kernel resets) sums the
- * n_partials_all partials at partials_all -- these and any written earlier, e.g. by mmvae_gemm_f32_sq -- in their fixed
+ * n_partials_all partials at partials_all -- these and any written earlier, e.g. by a GEMM's sq_partials -- in their fixed
  * order and fills state[] as mmvae_adam_prepare(flags | MMVAE_PREPARE_NORM) does.  Same numbers as the separate launches. */
 int mmvae_grad_sqnorm_ranges_prepare(int n_ranges, const float* const* grads, const int64_t* lens, float* partials,
                                      unsigned* ticket, int64_t n_partials_all, const float* partials_all, float max_norm,
@@ -468,7 +516,8 @@ typedef struct {
 int mmvae_sum_parts_batch(int n_jobs, const mmvae_sum_job* jobs, int64_t max_elems /* rows * cols of the largest job,
                           sizes the grid; 0 = unknown */, mmvae_stream_t stream);
 
-/* Unsplit GEMM that also leaves the sum of squares of everything it stores, one partial per output tile, in
+/* mmvae_gemm_planes_f32 with sq_partials != NULL (below; Ap = Bp = NULL for plain fp32 operands): an unsplit GEMM that
+ * also leaves the sum of squares of everything it stores, one partial per output tile, in
  * sq_partials[0 .. sq_capacity) (slots beyond the tiles it uses are zeroed): the weight-gradient GEMMs of the G-wide
  * layers write 82 MB each, and the gradient-norm pass of clip_grad_norm_ (cmmvae_model.py:126-129,203-209) would read
  * them all back.  The partials are summed with the other norm partials of the optimiser by mmvae_adam_prepare (fp64,
@@ -476,9 +525,6 @@ int mmvae_sum_parts_batch(int n_jobs, const mmvae_sum_job* jobs, int64_t max_ele
  * use mmvae_gemm_f32 and the norm pass); operands_regular != 0: A and B are 16-byte aligned with leading dimensions
  * that are multiples of 4 -- the count is then exact and the launch zero-fills nothing. */
 int mmvae_gemm_sq_partials(int layout, int M, int N, int K, int operands_regular);
-int mmvae_gemm_f32_sq(int layout, int M, int N, int K, float alpha, const float* A, int64_t lda, const float* B,
-                      int64_t ldb, float* C, int64_t ldc, const float* bias, unsigned flags, float* sq_partials,
-                      int64_t sq_capacity, mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Pre-split operands of the bf16x3 GEMMs (r3)
@@ -499,8 +545,9 @@ int mmvae_gemm_f32_sq(int layout, int M, int N, int K, float alpha, const float*
  * at least the count rounded up to 8 and the columns in between hold zeros -- mmvae_split_planes_f32 writes them --
  * because a rows-contiguous planes operand is fetched in whole 16-byte groups.
  *
- * mmvae_gemm_planes_f32 = mmvae_gemm_f32 (sq_partials == NULL) or mmvae_gemm_f32_sq (sq_partials != NULL) with
- * optional planes per operand.  Kernels exist for TN with A, B or both operands pre-split (late r5: A alone -- the
+ * mmvae_gemm_planes_f32 = mmvae_gemm_f32 (sq_partials == NULL), or the unsplit GEMM with norm partials above
+ * (sq_partials != NULL: sq_capacity > 0, no MMVAE_GEMM_RAW_SLABS, splitk and workspace ignored), with optional planes
+ * per operand.  Kernels exist for TN with A, B or both operands pre-split (late r5: A alone -- the
  * first layer's weight gradient dY^T x with the batch x read as fp32), for NT / NN with a pre-split A
  * and (r5) for NN with a pre-split B (the weights) against an fp32 A;
  * an operand whose planes cannot be used (other combinations, shapes off the wave-specialised kernel: K % 32 != 0,
@@ -517,55 +564,6 @@ int mmvae_gemm_planes_f32(int layout, int M, int N, int K, float alpha, const fl
                           int splitk, float* workspace, size_t workspace_bytes, float* sq_partials, int64_t sq_capacity,
                           mmvae_stream_t stream);
 int mmvae_gemm_planes_supported(int layout, int M, int N, int K, int splitk, int a_planes, int b_planes);
-/* mmvae_decoder_recon_rows_colsum_f32 with planes on either side of it:
- *   dP_planes != NULL  the epilogue also writes the three bf16 planes of dP (G % 8 == 0; dP itself may then be NULL):
- *                      the weight-gradient and input-gradient GEMMs that consume dP read it pre-split.
- *   hp != NULL         the decoder's hidden activations h pre-split (h may then be NULL): runs the wave-specialised
- *                      kernel (256-row tiles; col_part keeps its [mmvae_recon_row_tiles(rows)][G] layout, one partial
- *                      per 128-row half) when the shape fills the chip, otherwise falls back to the fp32 h if given.
- *                      (Measured slower than the two-workgroup kernel on fp32 h at C2: its epilogue is done by 4 of
- *                      the 8 waves; kept for shapes where the main loop dominates.)
- * Same products in the same order as the fp32 form. */
-int mmvae_decoder_recon_planes_f32(int rows, int x_rows, int G, int H, const float* h, int64_t ldh, const uint16_t* hp,
-                                   int64_t ldhp, int64_t h_plane_stride, const float* W, int64_t ldw, const float* bias,
-                                   const float* x, int64_t ldx, float* xhat, int64_t ldxhat, float* dP, int64_t lddp,
-                                   uint16_t* dP_planes, int64_t lddpp, int64_t dp_plane_stride, float* se_part,
-                                   float* col_part, mmvae_stream_t stream);
-/* (r5) mmvae_decoder_recon_planes_f32 with the WEIGHTS pre-split as well (Wp [G][ldwp] planes of W; taken together with hp,
- * otherwise W is read).  A K-sample program reads every weight tile from rows / 256 row tiles (20 at BASELINE config 3)
- * and splits it there each time; with both operands pre-split the stagers only move planes (LDS-DMA, no vector work).
- * The caller re-splits W after every optimiser step (mmvae_split_planes_f32, or the piggy-backed split of a layer tail).
- * replaces: the decoder's last nn.Linear + ReLU + mse_loss(sum) of modules/vae.py:140-145 (as above).
- * Same products in the same order as the fp32 form: bit-identical outputs. */
-int mmvae_decoder_recon_wplanes_f32(int rows, int x_rows, int G, int H, const float* h, int64_t ldh, const uint16_t* hp,
-                                    int64_t ldhp, int64_t h_plane_stride, const float* W, int64_t ldw, const uint16_t* Wp,
-                                    int64_t ldwp, int64_t w_plane_stride, const float* bias, const float* x, int64_t ldx,
-                                    float* xhat, int64_t ldxhat, float* dP, int64_t lddp, float* se_part, float* col_part,
-                                    mmvae_stream_t stream);
-/* mmvae_fc_epilogue_fwd / _bwd that also write the three bf16 planes of their output (d_out / the final dz_out; N even):
- * the layer tails that produce an operand of a G-wide weight-gradient GEMM (the decoder's last hidden activations, the
- * gradient at the expert encoder's first layer) split it on the way out. */
-int mmvae_fc_epilogue_fwd_planes(int B, int N, const float* in, int64_t ld_in, int n_slabs, const float* bias,
-                                 const mmvae_bn_params* bn, int training, int relu, const uint8_t* keep_mask,
-                                 float dropout_p, float* z_out, float* a_out, float* d_out, int64_t ld_out,
-                                 float* save_mean, float* save_invstd, float* workspace, size_t workspace_bytes,
-                                 uint16_t* d_planes, int64_t ldp, int64_t plane_stride, mmvae_stream_t stream);
-/* mmvae_fc_epilogue_fwd with a piggy-backed pass: extra workgroups of its second launch split the unrelated fp32
- * matrix sp_src [sp_rows, sp_cols] into its bf16 planes (as mmvae_split_planes_f32).  The engine splits its input
- * batch this way beside the first layer's tail: as a launch of its own the pass sits on the critical path of the step. */
-int mmvae_fc_epilogue_fwd_split(int B, int N, const float* in, int64_t ld_in, int n_slabs, const float* bias,
-                                const mmvae_bn_params* bn, int training, int relu, const uint8_t* keep_mask,
-                                float dropout_p, float* z_out, float* a_out, float* d_out, int64_t ld_out,
-                                float* save_mean, float* save_invstd, float* workspace, size_t workspace_bytes,
-                                int sp_rows, int sp_cols, const float* sp_src, int64_t sp_ld_src, uint16_t* sp_planes,
-                                int64_t sp_ld, int64_t sp_plane_stride, mmvae_stream_t stream);
-int mmvae_fc_epilogue_bwd_planes(int B, int N, const float* din, int64_t ld_in, int n_slabs, const float* addend,
-                                 const float* addend_a, const float* row_scale, const uint8_t* keep_mask, float dropout_p,
-                                 int relu, const float* a_act, const float* z, const float* gamma, const float* save_mean,
-                                 const float* save_invstd, int has_bn, float* dz_out, int64_t ld_out, float* dbias,
-                                 float* dgamma, float* dbeta, float* workspace, size_t workspace_bytes,
-                                 uint16_t* dz_planes, int64_t ldp, int64_t plane_stride, mmvae_stream_t stream);
-
 /* Grouped launch of independent small GEMMs (same math and layouts as mmvae_gemm_f32, exact-f32 MFMA, 64x64 tiles,
  * unsplit, alpha / bias / relu / accumulate epilogue): ONE grid covers the tiles of every job.  Used for the
  * weight-gradient GEMMs of the core (<= 1024-wide) layers of a backward pass -- replaces the per-parameter

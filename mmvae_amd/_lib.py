@@ -47,6 +47,27 @@ class BnParams(C.Structure):
     ]
 
 
+class Planes(C.Structure):
+    """mmvae_planes: the three bf16 planes of a matrix (p = None: absent)."""
+    _fields_ = [("p", _p), ("ld", _l), ("plane_stride", _l)]
+
+
+class ReconArgs(C.Structure):
+    """mmvae_recon_args: one mmvae_decoder_recon launch."""
+    _fields_ = [("rows", C.c_int32), ("x_rows", C.c_int32), ("G", C.c_int32), ("H", C.c_int32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32), ("h", _p), ("W", _p), ("bias", _p), ("x", _p), ("ldh", _l), ("ldw", _l),
+                ("ldx", _l), ("xhat", _p), ("dP", _p), ("se_part", _p), ("col_part", _p), ("ldxhat", _l), ("lddp", _l),
+                ("h_planes", Planes), ("W_planes", Planes), ("dP_planes", Planes)]
+
+
+class SplitJob(C.Structure):
+    """mmvae_split_job: the matrix a mmvae_fc_epilogue_fwd launch splits into planes on the side."""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("src", _p), ("ld_src", _l), ("planes", Planes)]
+
+
+RECON_H_KPAD = 1
+
+
 # name -> (restype, argtypes).  Kept in the order of include/mmvae_hip.h; tests/test_host_logic.py
 # (test_abi_header_symbols_are_exported_and_bound) checks that every
 # symbol the header declares is listed here and exported by the .so.
@@ -56,7 +77,6 @@ PROTOTYPES = {
     "mmvae_gemm_set_precision": (_i, [_i]),
     "mmvae_gemm_set_workgroup_cap": (_i, [_i]),
     "mmvae_adam_set_workgroups": (_i, [_i]),
-    "mmvae_recon_set_h_kpad": (_i, [_i]),
     "mmvae_adam_get_workgroups": (_i, []),
     "mmvae_gemm_set_x3w": (_i, [_i]),
     "mmvae_gemm_get_x3w": (_i, []),
@@ -65,18 +85,21 @@ PROTOTYPES = {
     "mmvae_gemm_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
     "mmvae_gemm_f32": (_i, [_i, _i, _i, _i, _f, _p, _l, _p, _l, _p, _l, _p, _u, _i, _p, _z, _p]),
     "mmvae_recon_tiles": (_i, [_i]),
-    "mmvae_decoder_recon_f32": (_i, [_i, _i, _i, _p, _l, _p, _l, _p, _p, _l, _p, _l, _p, _l, _p, _p]),
-    "mmvae_decoder_recon_rows_f32": (_i, [_i, _i, _i, _i, _p, _l, _p, _l, _p, _p, _l, _p, _l, _p, _l, _p, _p]),
     "mmvae_recon_row_tiles": (_i, [_i]),
-    "mmvae_decoder_recon_rows_colsum_f32": (_i, [_i, _i, _i, _i, _p, _l, _p, _l, _p, _p, _l, _p, _l, _p, _l, _p, _p, _p]),
+    "mmvae_decoder_recon": (_i, [C.POINTER(ReconArgs), _p]),
+    "mmvae_sizeof_planes": (_z, []),
+    "mmvae_sizeof_recon_args": (_z, []),
+    "mmvae_sizeof_split_job": (_z, []),
     "mmvae_fc_workspace_bytes": (_z, [_i, _i]),
     "mmvae_fc_epilogue_fwd": (
         _i,
-        [_i, _i, _p, _l, _i, _p, C.POINTER(BnParams), _i, _i, _p, _f, _p, _p, _p, _l, _p, _p, _p, _z, _p],
+        [_i, _i, _p, _l, _i, _p, C.POINTER(BnParams), _i, _i, _p, _f, _p, _p, _p, _l, _p, _p, _p, _z,
+         C.POINTER(Planes), C.POINTER(SplitJob), _p],
     ),
     "mmvae_fc_epilogue_bwd": (
         _i,
-        [_i, _i, _p, _l, _i, _p, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _i, _p, _l, _p, _p, _p, _p, _z, _p],
+        [_i, _i, _p, _l, _i, _p, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _i, _p, _l, _p, _p, _p, _p, _z,
+         C.POINTER(Planes), _p],
     ),
     "mmvae_layernorm_fwd": (_i, [_i, _i, _p, _l, _f, _p, _l, _p, _p, _p]),
     "mmvae_layernorm_bwd": (_i, [_i, _i, _p, _l, _p, _l, _p, _p, _l, _p]),
@@ -118,34 +141,12 @@ PROTOTYPES = {
     "mmvae_weighted_colsum_f32": (_i, [_i, _i, _p, _l, _p, _p, _p]),
     "mmvae_sum_parts_batch": (_i, [_i, _p, _l, _p]),
     "mmvae_gemm_sq_partials": (_i, [_i, _i, _i, _i, _i]),
-    "mmvae_gemm_f32_sq": (_i, [_i, _i, _i, _i, _f, _p, _l, _p, _l, _p, _l, _p, _u, _p, _l, _p]),
     "mmvae_split_planes_f32": (_i, [_i, _i, _p, _l, _p, _l, _l, _p]),
     "mmvae_gemm_planes_f32": (
         _i,
         [_i, _i, _i, _i, _f, _p, _l, _p, _l, _l, _p, _l, _p, _l, _l, _p, _l, _p, _u, _i, _p, _z, _p, _l, _p],
     ),
     "mmvae_gemm_planes_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
-    "mmvae_decoder_recon_planes_f32": (
-        _i,
-        [_i, _i, _i, _i, _p, _l, _p, _l, _l, _p, _l, _p, _p, _l, _p, _l, _p, _l, _p, _l, _l, _p, _p, _p],
-    ),
-    "mmvae_decoder_recon_wplanes_f32": (
-        _i,
-        [_i, _i, _i, _i, _p, _l, _p, _l, _l, _p, _l, _p, _l, _l, _p, _p, _l, _p, _l, _p, _l, _p, _p, _p],
-    ),
-    "mmvae_fc_epilogue_fwd_planes": (
-        _i,
-        [_i, _i, _p, _l, _i, _p, C.POINTER(BnParams), _i, _i, _p, _f, _p, _p, _p, _l, _p, _p, _p, _z, _p, _l, _l, _p],
-    ),
-    "mmvae_fc_epilogue_fwd_split": (
-        _i,
-        [_i, _i, _p, _l, _i, _p, C.POINTER(BnParams), _i, _i, _p, _f, _p, _p, _p, _l, _p, _p, _p, _z,
-         _i, _i, _p, _l, _p, _l, _l, _p],
-    ),
-    "mmvae_fc_epilogue_bwd_planes": (
-        _i,
-        [_i, _i, _p, _l, _i, _p, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _i, _p, _l, _p, _p, _p, _p, _z, _p, _l, _l, _p],
-    ),
     "mmvae_csr_to_dense_f32": (_i, [_i, _i, _l, _p, _p, _p, _p, _l, _p]),
     "mmvae_csr_to_dense_i32_f32": (_i, [_i, _i, _l, _p, _p, _p, _p, _l, _p]),
     "mmvae_csr_gather_rows_i64": (_i, [_i, _l, _l, _p, _p, _p, _p, _p, _l, _p, _p, _p]),

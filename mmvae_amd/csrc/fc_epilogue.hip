@@ -684,12 +684,20 @@ extern "C" size_t mmvae_fc_workspace_bytes(int B, int N) {
     return (size_t)3 * (size_t)ceil_div_i(B, RPC) * (size_t)N * sizeof(float);
 }
 
-static int fc_fwd_impl(int B, int N, const float* in, int64_t ld_in, int n_slabs, const float* bias,
-                       const mmvae_bn_params* bn, int training, int relu, const uint8_t* keep_mask, float dropout_p,
-                       float* z_out, float* a_out, float* d_out, int64_t ld_out, float* save_mean, float* save_invstd,
-                       float* workspace, size_t workspace_bytes, uint16_t* d_planes, int64_t ldp, int64_t pstride,
-                       mmvae_stream_t stream, int sp_rows = 0, int sp_cols = 0, const float* sp_src = nullptr,
-                       int64_t sp_ld_src = 0, uint16_t* sp_planes = nullptr, int64_t sp_ld = 0, int64_t sp_pstride = 0) {
+extern "C" int mmvae_fc_epilogue_fwd(int B, int N, const float* in, int64_t ld_in, int n_slabs, const float* bias,
+                                     const mmvae_bn_params* bn, int training, int relu, const uint8_t* keep_mask,
+                                     float dropout_p, float* z_out, float* a_out, float* d_out, int64_t ld_out,
+                                     float* save_mean, float* save_invstd, float* workspace, size_t workspace_bytes,
+                                     const mmvae_planes* d_pl, const mmvae_split_job* split, mmvae_stream_t stream) {
+    // (the planes output and the piggy-backed split job never shared an entry point: no launch carries both)
+    if ((d_pl && d_pl->p && split) || (split && !split->planes.p)) return MMVAE_ERR_ARG;
+    static const mmvae_planes no_planes = {nullptr, 0, 0};
+    const mmvae_planes dp = d_pl ? *d_pl : no_planes, sp = split ? split->planes : no_planes;
+    uint16_t *const d_planes = dp.p, *const sp_planes = sp.p;
+    const int64_t ldp = dp.ld, pstride = dp.plane_stride, sp_ld = sp.ld, sp_pstride = sp.plane_stride;
+    const int sp_rows = split ? split->rows : 0, sp_cols = split ? split->cols : 0;
+    const float* sp_src = split ? split->src : nullptr;
+    const int64_t sp_ld_src = split ? split->ld_src : 0;
     if (d_planes && (!d_out || N % 2 != 0 || ldp < N || ldp % 2 != 0 || pstride < (int64_t)B * ldp)) return MMVAE_ERR_ARG;
     if (sp_planes && (sp_rows <= 0 || sp_cols <= 0 || !sp_src || sp_ld_src < sp_cols || sp_ld < (sp_cols + 7) / 8 * 8 ||
                       sp_ld % 8 != 0 || sp_pstride % 8 != 0 || sp_pstride < (int64_t)sp_rows * sp_ld ||
@@ -761,44 +769,14 @@ static int fc_fwd_impl(int B, int N, const float* in, int64_t ld_in, int n_slabs
     return MMVAE_OK;
 }
 
-extern "C" int mmvae_fc_epilogue_fwd(int B, int N, const float* in, int64_t ld_in, int n_slabs, const float* bias,
-                                     const mmvae_bn_params* bn, int training, int relu, const uint8_t* keep_mask,
-                                     float dropout_p, float* z_out, float* a_out, float* d_out, int64_t ld_out,
-                                     float* save_mean, float* save_invstd, float* workspace, size_t workspace_bytes,
-                                     mmvae_stream_t stream) {
-    return fc_fwd_impl(B, N, in, ld_in, n_slabs, bias, bn, training, relu, keep_mask, dropout_p, z_out, a_out, d_out, ld_out,
-                       save_mean, save_invstd, workspace, workspace_bytes, nullptr, 0, 0, stream);
-}
-
-extern "C" int mmvae_fc_epilogue_fwd_planes(int B, int N, const float* in, int64_t ld_in, int n_slabs, const float* bias,
-                                            const mmvae_bn_params* bn, int training, int relu, const uint8_t* keep_mask,
-                                            float dropout_p, float* z_out, float* a_out, float* d_out, int64_t ld_out,
-                                            float* save_mean, float* save_invstd, float* workspace,
-                                            size_t workspace_bytes, uint16_t* d_planes, int64_t ldp, int64_t plane_stride,
-                                            mmvae_stream_t stream) {
-    return fc_fwd_impl(B, N, in, ld_in, n_slabs, bias, bn, training, relu, keep_mask, dropout_p, z_out, a_out, d_out, ld_out,
-                       save_mean, save_invstd, workspace, workspace_bytes, d_planes, ldp, plane_stride, stream);
-}
-
-extern "C" int mmvae_fc_epilogue_fwd_split(int B, int N, const float* in, int64_t ld_in, int n_slabs, const float* bias,
-                                           const mmvae_bn_params* bn, int training, int relu, const uint8_t* keep_mask,
-                                           float dropout_p, float* z_out, float* a_out, float* d_out, int64_t ld_out,
-                                           float* save_mean, float* save_invstd, float* workspace, size_t workspace_bytes,
-                                           int sp_rows, int sp_cols, const float* sp_src, int64_t sp_ld_src,
-                                           uint16_t* sp_planes, int64_t sp_ld, int64_t sp_plane_stride,
-                                           mmvae_stream_t stream) {
-    if (!sp_planes) return MMVAE_ERR_ARG;
-    return fc_fwd_impl(B, N, in, ld_in, n_slabs, bias, bn, training, relu, keep_mask, dropout_p, z_out, a_out, d_out, ld_out,
-                       save_mean, save_invstd, workspace, workspace_bytes, nullptr, 0, 0, stream, sp_rows, sp_cols, sp_src,
-                       sp_ld_src, sp_planes, sp_ld, sp_plane_stride);
-}
-
-static int fc_bwd_impl(int B, int N, const float* din, int64_t ld_in, int n_slabs, const float* addend,
-                       const float* addend_a, const float* row_scale, const uint8_t* keep_mask, float dropout_p, int relu,
-                       const float* a_act, const float* z, const float* gamma, const float* save_mean,
-                       const float* save_invstd, int has_bn, float* dz_out, int64_t ld_out, float* dbias, float* dgamma,
-                       float* dbeta, float* workspace, size_t workspace_bytes, uint16_t* dz_planes, int64_t ldp,
-                       int64_t pstride, mmvae_stream_t stream) {
+extern "C" int mmvae_fc_epilogue_bwd(int B, int N, const float* din, int64_t ld_in, int n_slabs, const float* addend,
+                                     const float* addend_a, const float* row_scale, const uint8_t* keep_mask,
+                                     float dropout_p, int relu, const float* a_act, const float* z, const float* gamma,
+                                     const float* save_mean, const float* save_invstd, int has_bn, float* dz_out,
+                                     int64_t ld_out, float* dbias, float* dgamma, float* dbeta, float* workspace,
+                                     size_t workspace_bytes, const mmvae_planes* dz_pl, mmvae_stream_t stream) {
+    uint16_t* const dz_planes = dz_pl ? dz_pl->p : nullptr;
+    const int64_t ldp = dz_pl ? dz_pl->ld : 0, pstride = dz_pl ? dz_pl->plane_stride : 0;
     if (dz_planes && (!dz_out || N % 2 != 0 || ldp < N || ldp % 2 != 0 || pstride < (int64_t)B * ldp)) return MMVAE_ERR_ARG;
     if (B <= 0 || N <= 0 || !din || n_slabs < 1 || ld_in < N || ld_out < N) return MMVAE_ERR_ARG;
     if (relu && !a_act) return MMVAE_ERR_ARG;
@@ -850,30 +828,6 @@ static int fc_bwd_impl(int B, int N, const float* din, int64_t ld_in, int n_slab
     }
     MMVAE_LAUNCH_CHECK();
     return MMVAE_OK;
-}
-
-extern "C" int mmvae_fc_epilogue_bwd(int B, int N, const float* din, int64_t ld_in, int n_slabs, const float* addend,
-                                     const float* addend_a, const float* row_scale, const uint8_t* keep_mask, float dropout_p, int relu,
-                                     const float* a_act, const float* z, const float* gamma, const float* save_mean,
-                                     const float* save_invstd, int has_bn, float* dz_out, int64_t ld_out, float* dbias,
-                                     float* dgamma, float* dbeta, float* workspace, size_t workspace_bytes,
-                                     mmvae_stream_t stream) {
-    return fc_bwd_impl(B, N, din, ld_in, n_slabs, addend, addend_a, row_scale, keep_mask, dropout_p, relu, a_act, z, gamma,
-                       save_mean, save_invstd, has_bn, dz_out, ld_out, dbias, dgamma, dbeta, workspace, workspace_bytes,
-                       nullptr, 0, 0, stream);
-}
-
-extern "C" int mmvae_fc_epilogue_bwd_planes(int B, int N, const float* din, int64_t ld_in, int n_slabs,
-                                            const float* addend, const float* addend_a, const float* row_scale,
-                                            const uint8_t* keep_mask, float dropout_p, int relu, const float* a_act,
-                                            const float* z, const float* gamma, const float* save_mean,
-                                            const float* save_invstd, int has_bn, float* dz_out, int64_t ld_out,
-                                            float* dbias, float* dgamma, float* dbeta, float* workspace,
-                                            size_t workspace_bytes, uint16_t* dz_planes, int64_t ldp,
-                                            int64_t plane_stride, mmvae_stream_t stream) {
-    return fc_bwd_impl(B, N, din, ld_in, n_slabs, addend, addend_a, row_scale, keep_mask, dropout_p, relu, a_act, z, gamma,
-                       save_mean, save_invstd, has_bn, dz_out, ld_out, dbias, dgamma, dbeta, workspace, workspace_bytes,
-                       dz_planes, ldp, plane_stride, stream);
 }
 
 extern "C" int mmvae_layernorm_fwd(int B, int N, const float* x, int64_t ldx, float eps, float* y, int64_t ldy,

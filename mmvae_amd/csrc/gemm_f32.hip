@@ -20,7 +20,7 @@
 //   * Workgroup ids are remapped so each XCD (private 4 MiB L2) gets a contiguous run of tiles, M fastest:
 //     neighbouring tiles share the same weight / activation panel in that XCD's L2.
 //   * The last decoder layer has its own epilogue: bias + ReLU + (xhat - x)^2 + dP, with the per-cell squared
-//     error reduced across the wavefront by shuffles (mmvae_decoder_recon_f32).
+//     error reduced across the wavefront by shuffles (mmvae_decoder_recon).
 #include "gemm_dev.h"
 
 namespace {
@@ -1046,7 +1046,7 @@ static bool planes_usable(int layout, bool is_a, int M, int N, int K, const uint
     return 3 * pstride * 2 < (int64_t)0xFFFFFFFF;
 }
 
-// Tiles of the unsplit launch the library would make for this shape (= partial sums mmvae_gemm_f32_sq writes).
+// Tiles of the unsplit launch the library would make for this shape (= partial sums a launch with sq_partials writes).
 static int sq_tiles(int layout, int M, int N, int K, bool aligned2) {
     int tile_id, sk;
     plan(layout, M, N, K, &tile_id, &sk);
@@ -1066,14 +1066,6 @@ extern "C" int mmvae_gemm_sq_partials(int layout, int M, int N, int K, int opera
     (void)operands_regular;  // (alignment no longer decides the tile shape; kept for ABI stability)
     if (x3_vec_ok(layout, M, N, false)) return a;
     return a > b ? a : b;
-}
-
-extern "C" int mmvae_gemm_f32_sq(int layout, int M, int N, int K, float alpha, const float* A, int64_t lda,
-                                 const float* B, int64_t ldb, float* C, int64_t ldc, const float* bias, unsigned flags,
-                                 float* sq_partials, int64_t sq_capacity, mmvae_stream_t stream) {
-    if (!sq_partials || sq_capacity <= 0 || (flags & MMVAE_GEMM_RAW_SLABS)) return MMVAE_ERR_ARG;
-    return gemm_f32_impl(layout, M, N, K, alpha, A, lda, B, ldb, C, ldc, bias, flags, 1, nullptr, 0, sq_partials,
-                         sq_capacity, stream);
 }
 
 extern "C" int mmvae_gemm_planes_f32(int layout, int M, int N, int K, float alpha, const float* A, int64_t lda,
@@ -1363,32 +1355,29 @@ extern "C" int mmvae_gemm_set_workgroup_cap(int max_workgroups) {
 
 extern "C" int mmvae_recon_row_tiles(int rows) { return rows > 0 ? ceil_div_i(rows, 128) : 0; }
 
-extern "C" int mmvae_decoder_recon_rows_f32(int rows, int x_rows, int G, int H, const float* h, int64_t ldh,
-                                            const float* W, int64_t ldw, const float* bias, const float* x, int64_t ldx,
-                                            float* xhat, int64_t ldxhat, float* dP, int64_t lddp, float* se_part,
-                                            mmvae_stream_t stream) {
-    return mmvae_decoder_recon_rows_colsum_f32(rows, x_rows, G, H, h, ldh, W, ldw, bias, x, ldx, xhat, ldxhat, dP, lddp,
-                                               se_part, nullptr, stream);
-}
+extern "C" size_t mmvae_sizeof_planes(void) { return sizeof(mmvae_planes); }
+extern "C" size_t mmvae_sizeof_recon_args(void) { return sizeof(mmvae_recon_args); }
+extern "C" size_t mmvae_sizeof_split_job(void) { return sizeof(mmvae_split_job); }
 
-// h pre-split (hp != NULL): the wave-specialised kernel with LDS-DMA staging of h (mmvae_decoder_recon_planes_f32)
-// Launch state (host side, like the workgroup cap): the caller vouches that h has ZERO columns from H up to the next
-// multiple of the 32-wide k-tile inside its leading dimension and that W's rows may be read that far (finite values: the
-// next row, or the slack behind an optimiser arena).  A hidden width that is not a multiple of 32 (1000) then runs the
-// pipelined kernels over the padded K -- what lies beyond H meets exact zeros -- instead of the guarded loop
-// (242 against 123 us at C2's sizes).
-static int g_recon_kpad = 0;
-extern "C" int mmvae_recon_set_h_kpad(int on) {
-    g_recon_kpad = on ? 1 : 0;
-    return MMVAE_OK;
-}
-
-static int decoder_recon_impl(int rows, int x_rows, int G, int H, const float* h, int64_t ldh, const uint16_t* hp,
-                              int64_t ldhp, int64_t h_pstride, const float* W, int64_t ldw, const uint16_t* Wp,
-                              int64_t ldwp, int64_t w_pstride, const float* bias,
-                              const float* x, int64_t ldx, float* xhat, int64_t ldxhat, float* dP, int64_t lddp,
-                              uint16_t* dPp, int64_t lddpp, int64_t dp_pstride, float* se_part, float* col_part,
-                              mmvae_stream_t stream) {
+// h_planes: the wave-specialised kernel with LDS-DMA staging of h.  MMVAE_RECON_H_KPAD: the caller vouches that h has
+// ZERO columns from H up to the next multiple of the 32-wide k-tile inside its leading dimension and that W's rows may be
+// read that far (finite values: the next row, or the slack behind an optimiser arena).  A hidden width that is not a
+// multiple of 32 (1000) then runs the pipelined kernels over the padded K -- what lies beyond H meets exact zeros --
+// instead of the guarded loop (242 against 123 us at C2's sizes).
+extern "C" int mmvae_decoder_recon(const mmvae_recon_args* args, mmvae_stream_t stream) {
+    if (!args || (args->flags & ~MMVAE_RECON_H_KPAD)) return MMVAE_ERR_ARG;
+    const mmvae_recon_args& r = *args;
+    // (the weight planes and the gradient planes never shared an entry point: no launch carries both)
+    if (r.W_planes.p && r.dP_planes.p) return MMVAE_ERR_ARG;
+    const int rows = r.rows, x_rows = r.x_rows, G = r.G;
+    int H = r.H;
+    const float *h = r.h, *W = r.W, *bias = r.bias, *x = r.x;
+    float *xhat = r.xhat, *dP = r.dP, *se_part = r.se_part, *col_part = r.col_part;
+    const int64_t ldh = r.ldh, ldw = r.ldw, ldx = r.ldx, ldxhat = r.ldxhat, lddp = r.lddp;
+    const uint16_t *hp = r.h_planes.p, *Wp = r.W_planes.p;
+    uint16_t* dPp = r.dP_planes.p;
+    const int64_t ldhp = r.h_planes.ld, h_pstride = r.h_planes.plane_stride, ldwp = r.W_planes.ld,
+                  w_pstride = r.W_planes.plane_stride, lddpp = r.dP_planes.ld, dp_pstride = r.dP_planes.plane_stride;
     if (rows <= 0 || x_rows <= 0 || rows % x_rows != 0 || G <= 0 || H <= 0 || (!h && !hp) || !W || !x || !se_part)
         return MMVAE_ERR_ARG;
     if (dPp && (G % 8 != 0 || lddpp < G || lddpp % 8 != 0 || dp_pstride % 8 != 0 || dp_pstride < (int64_t)rows * lddpp ||
@@ -1403,7 +1392,7 @@ static int decoder_recon_impl(int rows, int x_rows, int G, int H, const float* h
     g.bias = bias;
     g.lda = ldh;
     g.ldb = ldw;
-    if (g_recon_kpad && H % X3_BK != 0 && h && !hp && ldh >= (int64_t)ceil_div_i(H, X3_BK) * X3_BK)
+    if ((r.flags & MMVAE_RECON_H_KPAD) && H % X3_BK != 0 && h && !hp && ldh >= (int64_t)ceil_div_i(H, X3_BK) * X3_BK)
         H = ceil_div_i(H, X3_BK) * X3_BK;  // (zero columns of h against whatever follows a row of W)
     g.M = rows;
     g.N = G;
@@ -1465,39 +1454,3 @@ static int decoder_recon_impl(int rows, int x_rows, int G, int H, const float* h
     return launch_gemm_forms<FORM_KC, FORM_KC, EPI_RECON>(tile_id, g, g.mt * g.nt, (hipStream_t)stream);
 }
 
-extern "C" int mmvae_decoder_recon_rows_colsum_f32(int rows, int x_rows, int G, int H, const float* h, int64_t ldh,
-                                                   const float* W, int64_t ldw, const float* bias, const float* x,
-                                                   int64_t ldx, float* xhat, int64_t ldxhat, float* dP, int64_t lddp,
-                                                   float* se_part, float* col_part, mmvae_stream_t stream) {
-    return decoder_recon_impl(rows, x_rows, G, H, h, ldh, nullptr, 0, 0, W, ldw, nullptr, 0, 0, bias, x, ldx, xhat, ldxhat, dP,
-                              lddp, nullptr, 0, 0, se_part, col_part, stream);
-}
-
-extern "C" int mmvae_decoder_recon_planes_f32(int rows, int x_rows, int G, int H, const float* h, int64_t ldh,
-                                              const uint16_t* hp, int64_t ldhp, int64_t h_plane_stride, const float* W,
-                                              int64_t ldw, const float* bias, const float* x, int64_t ldx, float* xhat,
-                                              int64_t ldxhat, float* dP, int64_t lddp, uint16_t* dP_planes,
-                                              int64_t lddpp, int64_t dp_plane_stride, float* se_part, float* col_part,
-                                              mmvae_stream_t stream) {
-    return decoder_recon_impl(rows, x_rows, G, H, h, ldh, hp, ldhp, h_plane_stride, W, ldw, nullptr, 0, 0, bias, x, ldx, xhat,
-                              ldxhat, dP, lddp, dP_planes, lddpp, dp_plane_stride, se_part, col_part, stream);
-}
-
-// (r5) ... with the weights pre-split as well (Wp; used together with hp, otherwise W is read): K-sample programs read
-// every weight tile from rows / 256 row tiles -- 20 at C3 -- and split it there each time
-extern "C" int mmvae_decoder_recon_wplanes_f32(int rows, int x_rows, int G, int H, const float* h, int64_t ldh,
-                                               const uint16_t* hp, int64_t ldhp, int64_t h_plane_stride, const float* W,
-                                               int64_t ldw, const uint16_t* Wp, int64_t ldwp, int64_t w_plane_stride,
-                                               const float* bias, const float* x, int64_t ldx, float* xhat, int64_t ldxhat,
-                                               float* dP, int64_t lddp, float* se_part, float* col_part,
-                                               mmvae_stream_t stream) {
-    return decoder_recon_impl(rows, x_rows, G, H, h, ldh, hp, ldhp, h_plane_stride, W, ldw, Wp, ldwp, w_plane_stride, bias, x,
-                              ldx, xhat, ldxhat, dP, lddp, nullptr, 0, 0, se_part, col_part, stream);
-}
-
-extern "C" int mmvae_decoder_recon_f32(int B, int G, int H, const float* h, int64_t ldh, const float* W, int64_t ldw,
-                                       const float* bias, const float* x, int64_t ldx, float* xhat, int64_t ldxhat,
-                                       float* dP, int64_t lddp, float* se_part, mmvae_stream_t stream) {
-    return mmvae_decoder_recon_rows_f32(B, B, G, H, h, ldh, W, ldw, bias, x, ldx, xhat, ldxhat, dP, lddp, se_part,
-                                        stream);
-}

@@ -1254,7 +1254,7 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
             # a hidden width off the 32-wide k-tile (1000): the fused kernel's pipelined loop needs whole k-tiles --
             # it gets a copy of h in a buffer padded with zero columns (a 2 MB pass: ~4 us) and runs over the padded
             # K; the weights' rows are read on into the next row / the arena's slack, against those zeros
-            # (mmvae_recon_set_h_kpad; the guarded loop it replaces: 242 against 123 us at C2's sizes)
+            # (MMVAE_RECON_H_KPAD; the guarded loop it replaces: 242 against 123 us at C2's sizes)
             Kp = (last.n_in + 31) // 32 * 32
             hpad = eng.buf(f"hpad.{R}.{last.n_in}", (R, Kp))
             # (reductions / grouped GEMMs queued so far wait for their own flush)
@@ -1263,20 +1263,12 @@ class _Plan(PlanEmit, PlanAdversaries, PlanRun):
             self._flush_sums()
             self._sum_jobs, self._gemm_jobs = pending, pending_g
             h_in, ld_h, kpad = hpad, Kp, True
-        self._emit(lib.mmvae_decoder_recon_rows_colsum_f32, R, B, G, last.n_in, _p(h_in), ld_h, _p(last.W), last.n_in,
-                   _p(last.b), _p(self.x), self.ldx, None, 0, _p(self.dP), self.ldp, _p(self.se_part),
-                   _p(self.dp_colpart), probe=("dec_l2_recon", 2.0 * R * G * last.n_in))
-        if kpad:  # the launch state brackets the launch
-            launch = self._cur.pop()
-
-            def recon_kpad(launch=launch):
-                lib.mmvae_recon_set_h_kpad(1)
-                try:
-                    launch()
-                finally:
-                    lib.mmvae_recon_set_h_kpad(0)
-
-            self._cur.append(recon_kpad)
+        # (built once and kept on the plan for its lifetime, like a layer's _bnp)
+        self._recon_args = _lib.ReconArgs(
+            rows=R, x_rows=B, G=G, H=last.n_in, flags=_lib.RECON_H_KPAD if kpad else 0, h=_p(h_in), ldh=ld_h,
+            W=_p(last.W), ldw=last.n_in, bias=_p(last.b), x=_p(self.x), ldx=self.ldx, dP=_p(self.dP), lddp=self.ldp,
+            se_part=_p(self.se_part), col_part=_p(self.dp_colpart))
+        self._emit(lib.mmvae_decoder_recon, self._recon_args, probe=("dec_l2_recon", 2.0 * R * G * last.n_in))
         self.probe_meta["dec_l2_recon"].update(bound="mfma", cus=0, planes="",
                                                shape=f"NT {R}x{G}x{last.n_in} + reconstruction epilogue")
         self._mark("reconstruction done")

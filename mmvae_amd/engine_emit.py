@@ -113,7 +113,7 @@ class PlanEmit:
     def _fuse_sqnorm(self, layout, M, N, K, alpha, A, lda, Bm, ldb, Cm, ldc, bias, flags, side_cap: int = 0,
                      on_side: bool = True, planes=None, stream=None) -> bool:
         """Unsplit weight-gradient GEMM straight into a gradient arena: let its epilogue also leave the partial sums of
-        squares of what it stores (mmvae_gemm_f32_sq), so that the clip's norm pass does not read the 82 MB back.  Only
+        squares of what it stores (sq_partials), so that the clip's norm pass does not read the 82 MB back.  Only
         without a gradient exchange: under data parallelism the norm is that of the REDUCED gradients.  side_cap: capped
         to that many workgroups, on the branch `stream` (default the side stream) unless on_side=False."""
         eng = self.eng
@@ -147,7 +147,7 @@ class PlanEmit:
         """Emit one GEMM launch.  planes: (A planes or None, B planes or None) -- pre-split forms of the operands
         (_PlaneBuf); the fp32 pointers stay the library's fallback for shapes the planes kernels do not take.  Cm None:
         the shared slab buffer; use_ws: the shared split-K workspace; sq: (pointer, count) of the norm-partial slots its
-        epilogue fills (mmvae_gemm_f32_sq).  cap: the persistent grid capped to `cap` workgroups -- the CUs left over serve
+        epilogue fills (sq_partials).  cap: the persistent grid capped to `cap` workgroups -- the CUs left over serve
         another branch -- on branch `stream` (None: the current stream), forked from the main stream first; joined by the
         next cut / _join()."""
         plan, lib = self, self.lib
@@ -158,15 +158,8 @@ class PlanEmit:
         def launch_gemm():
             ws = (plan.ws.data_ptr(), plan.ws.numel() * 4) if use_ws else (None, 0)
             c_ptr = _p(Cm) if Cm is not None else plan.slab.data_ptr()
-            if planes:
-                rc = lib.mmvae_gemm_planes_f32(layout, M, N, K, alpha, _p(A), lda, *ap, _p(Bm), ldb, *bp, c_ptr, ldc,
-                                               _p(bias), flags | SLACK, sk, *ws, *sq_args, _s())
-            elif sq:
-                rc = lib.mmvae_gemm_f32_sq(layout, M, N, K, alpha, _p(A), lda, _p(Bm), ldb, c_ptr, ldc, _p(bias),
-                                           flags | SLACK, *sq, _s())
-            else:
-                rc = lib.mmvae_gemm_f32(layout, M, N, K, alpha, _p(A), lda, _p(Bm), ldb, c_ptr, ldc, _p(bias),
-                                        flags | SLACK, sk, *ws, _s())
+            rc = lib.mmvae_gemm_planes_f32(layout, M, N, K, alpha, _p(A), lda, *ap, _p(Bm), ldb, *bp, c_ptr, ldc,
+                                           _p(bias), flags | SLACK, sk, *ws, *sq_args, _s())
             if rc != 0:
                 raise _lib.HipLibraryError(f"GEMM launch failed with code {rc} (layout {layout}, {M}x{N}x{K})")
 
@@ -296,7 +289,7 @@ class PlanEmit:
 
     def _next_x_split_job(self, l: _LayerRef, rows: int):
         """The next piece of the input batch's split for a layer whose tail is a column-kernel launch (fwd_layer's slab
-        path), or None."""
+        path) as the mmvae_split_job of that launch, or None."""
         if not self._x_split_jobs:
             return None
         p_drop = l.p if self.mode == "train" else 0.0
@@ -304,7 +297,8 @@ class PlanEmit:
             return None  # this layer's tail is the row kernel
         if l.bn is None and p_drop == 0 and self._plan_gemm(NT, rows, l.n_out, l.n_in) == 1:
             return None  # this layer's tail is fused into its GEMM
-        return self._x_split_jobs.pop(0)
+        job = self._x_split_jobs.pop(0)  # (rows, cols, src, ld_src, planes pointer, ld, plane stride)
+        return _lib.SplitJob(*job[:4], _lib.Planes(*job[4:]))
 
     def _fork(self, stream=None):
         """A branch stream (default: the side stream) waits for everything enqueued so far on the main stream."""
@@ -423,18 +417,15 @@ class PlanEmit:
                                 _p(bn.num_batches_tracked), float(bn.momentum), float(bn.eps))
             l._bnp = bnp  # keep the struct alive for the lifetime of the plan
         plan = self
+        # d_planes: the layer tail also leaves the bf16 planes of its output; split_job: extra workgroups of the tail split
+        # an unrelated matrix (the input batch).  One or the other: the library refuses a launch with both.
+        d_planes = _lib.Planes(*planes_out.args()) if planes_out is not None else None
 
         def call():
-            args = (rows, l.n_out, slabs_from.data_ptr() if slabs_from is not None else plan.slab.data_ptr(), l.n_out, S, _p(l.b),
-                    C.byref(bnp) if bnp is not None else None, int(training), int(relu),
-                    _p(mask), p_drop, _p(l.z), _p(a_out), _p(d_out), l.n_out, _p(l.mean), _p(l.invstd),
-                    plan.fcws.data_ptr(), plan.fcws.numel() * 4)
-            if split_job is not None:  # extra workgroups of the tail split an unrelated matrix (the input batch)
-                rc = plan.lib.mmvae_fc_epilogue_fwd_split(*args, *split_job, _s())
-            elif planes_out is not None:  # the layer tail also leaves the bf16 planes of its output
-                rc = plan.lib.mmvae_fc_epilogue_fwd_planes(*args, *planes_out.args(), _s())
-            else:
-                rc = plan.lib.mmvae_fc_epilogue_fwd(*args, _s())
+            rc = plan.lib.mmvae_fc_epilogue_fwd(
+                rows, l.n_out, slabs_from.data_ptr() if slabs_from is not None else plan.slab.data_ptr(), l.n_out, S, _p(l.b),
+                bnp, int(training), int(relu), _p(mask), p_drop, _p(l.z), _p(a_out), _p(d_out), l.n_out, _p(l.mean),
+                _p(l.invstd), plan.fcws.data_ptr(), plan.fcws.numel() * 4, d_planes, split_job, _s())
             if rc != 0:
                 raise _lib.HipLibraryError(f"mmvae_fc_epilogue_fwd failed with code {rc}")
 
@@ -483,6 +474,7 @@ class PlanEmit:
         (the K-sample bound's weights, applied where the slabs are summed)."""
         rows = l.rows
         dw_planes = (dz_planes, inp_planes) if (dz_planes is not None and (inp_planes is not None or self.x_fp32_dw1)) else None
+        dz_pl = _lib.Planes(*dz_planes.args()) if dw_planes is not None else None  # the column kernel also splits .dz
         plan = self
         relu_src = l.a if l.a is not None else l.d
         has_bn = l.bn is not None
@@ -499,14 +491,12 @@ class PlanEmit:
             ws = own_ws if own_ws is not None else plan.fcws
             # `addend` is a gradient on the hidden representation = the activation BEFORE dropout: it bypasses the mask
             mask, relu = (None, False) if after_ln else (l.mask, l.relu)
-            args = (rows, l.n_out, din_ptr, l.n_out, S_in, None, _p(addend), _p(row_scale), _p(mask), l.p, int(relu),
-                    _p(relu_src) if relu else None, _p(l.z), _p(l.bn.weight) if has_bn else None, _p(l.mean),
-                    _p(l.invstd), int(has_bn), _p(l.dz), l.n_out, _p(l.gb) if own_ws is None else None,
-                    _p(l.ggamma) if has_bn else None, _p(l.gbeta) if has_bn else None, ws.data_ptr(), ws.numel() * 4)
-            if dw_planes is not None:
-                rc = plan.lib.mmvae_fc_epilogue_bwd_planes(*args, *dz_planes.args(), _s())
-            else:
-                rc = plan.lib.mmvae_fc_epilogue_bwd(*args, _s())
+            rc = plan.lib.mmvae_fc_epilogue_bwd(
+                rows, l.n_out, din_ptr, l.n_out, S_in, None, _p(addend), _p(row_scale), _p(mask), l.p, int(relu),
+                _p(relu_src) if relu else None, _p(l.z), _p(l.bn.weight) if has_bn else None, _p(l.mean),
+                _p(l.invstd), int(has_bn), _p(l.dz), l.n_out, _p(l.gb) if own_ws is None else None,
+                _p(l.ggamma) if has_bn else None, _p(l.gbeta) if has_bn else None, ws.data_ptr(), ws.numel() * 4,
+                dz_pl, _s())
             if rc != 0:
                 raise _lib.HipLibraryError(f"mmvae_fc_epilogue_bwd failed with code {rc}")
 
@@ -580,7 +570,7 @@ class PlanEmit:
         def call():
             rc = plan.lib.mmvae_fc_epilogue_bwd(rows, N, _p(pair), N, 1, None, None, None, None, 0.0, 0, None, None,
                                                 None, None, None, 0, None, N, None, None, None, ws.data_ptr(),
-                                                ws.numel() * 4, _s())
+                                                ws.numel() * 4, None, _s())
             if rc != 0:
                 raise _lib.HipLibraryError(f"mmvae_fc_epilogue_bwd (stacked column sums) failed with code {rc}")
 
@@ -596,7 +586,7 @@ class PlanEmit:
             ws = own_ws if own_ws is not None else plan.fcws
             rc = plan.lib.mmvae_fc_epilogue_bwd(rows, N, _p(din), N, 1, _p(addend), None, _p(row_scale), None, 0.0, 0, None, None,
                                                 None, None, None, 0, _p(dz_out), N, _p(dbias) if own_ws is None else None,
-                                                None, None, ws.data_ptr(), ws.numel() * 4, _s())
+                                                None, None, ws.data_ptr(), ws.numel() * 4, None, _s())
             if rc != 0:
                 raise _lib.HipLibraryError(f"mmvae_fc_epilogue_bwd (column sum) failed with code {rc}")
 

@@ -124,7 +124,8 @@ def gemm(
 def gemm_sq(layout: int, a: torch.Tensor, b: torch.Tensor, *, out: Optional[torch.Tensor] = None,
             bias: Optional[torch.Tensor] = None, alpha: float = 1.0, accumulate: bool = False):
     """Unsplit GEMM (as gemm()) that also returns the per-tile partial sums of squares of what it stored
-    (mmvae_gemm_f32_sq): (out, partials) with partials.sum() == (out ** 2).sum() up to fp32 rounding."""
+    (mmvae_gemm_planes_f32 with sq_partials): (out, partials) with partials.sum() == (out ** 2).sum() up to fp32
+    rounding."""
     lib = _lib.load()
     _chk(a, "a"), _chk(b, "b"), _chk(bias, "bias")
     ar, ac, lda = _mat(a, "a")
@@ -138,8 +139,9 @@ def gemm_sq(layout: int, a: torch.Tensor, b: torch.Tensor, *, out: Optional[torc
         raise ValueError("gemm_sq: this shape is planned as a split-K launch")
     partials = torch.empty(n, dtype=torch.float32, device=a.device)
     flags = GEMM_ACCUMULATE if accumulate else 0
-    _lib.check(lib.mmvae_gemm_f32_sq(layout, M, N, K, alpha, _ptr(a), lda, _ptr(b), ldb, _ptr(out), _mat(out, "out")[2],
-                                     _ptr(bias), flags, _ptr(partials), n, _stream()), "mmvae_gemm_f32_sq")
+    _lib.check(lib.mmvae_gemm_planes_f32(layout, M, N, K, alpha, _ptr(a), lda, None, 0, 0, _ptr(b), ldb, None, 0, 0,
+                                         _ptr(out), _mat(out, "out")[2], _ptr(bias), flags, 1, None, 0, _ptr(partials), n,
+                                         _stream()), "mmvae_gemm_planes_f32")
     return out, partials
 
 
@@ -156,10 +158,18 @@ class Planes:
     def ptr(self):
         return self.data.data_ptr()
 
+    def as_c(self) -> _lib.Planes:
+        """the mmvae_planes struct of the C-ABI"""
+        return _lib.Planes(self.ptr(), self.ld, self.plane_stride)
+
     def to_float(self) -> torch.Tensor:
         """p0 + p1 + p2 as fp32 (exactly the matrix that was split; tests)."""
         planes = (self.data[:, : self.rows, : self.cols].to(torch.int32) << 16).view(torch.float32)
         return (planes[0] + planes[1]) + planes[2]
+
+
+def _c_planes(pl: Optional[Planes]) -> _lib.Planes:
+    return pl.as_c() if pl is not None else _lib.Planes()
 
 
 def split_planes(src: torch.Tensor, out: Optional[Planes] = None) -> Planes:
@@ -277,8 +287,8 @@ def decoder_recon(
 ):
     """Fused last decoder layer + squared error.  h [R,H] (R = K*B rows), W [G,H], x [B,G].
     h_kpad: h is a view of a buffer whose columns H .. round_up(H, 32) - 1 are ZERO and W's rows may be read that far
-    (mmvae_recon_set_h_kpad): a hidden width that is not a multiple of 32 then takes the pipelined kernels.
-    h_planes: the pre-split h (mmvae_decoder_recon_planes_f32; h stays the fallback).
+    (MMVAE_RECON_H_KPAD, for this call): a hidden width that is not a multiple of 32 then takes the pipelined kernels.
+    h_planes: the pre-split h (h stays the fallback); W_planes: the weights pre-split as well, taken together with h_planes.
     Returns (xhat [R,G] | None, dP [R,G] | None, se_part [tiles, R]).  col_part [recon_row_tiles(R), G] (optional):
     receives the column sums of dP per row tile (their sum over the tiles is the bias gradient when K = 1)."""
     lib = _lib.load()
@@ -299,38 +309,16 @@ def decoder_recon(
     lddp = _mat(dP, "dP")[2] if dP is not None else 0
     if col_part is not None and (tuple(col_part.shape) != (lib.mmvae_recon_row_tiles(R), G) or not col_part.is_contiguous()):
         raise ValueError(f"decoder_recon: col_part must be a contiguous [{lib.mmvae_recon_row_tiles(R)}, {G}] tensor")
-    if W_planes is not None:  # weights pre-split as well (mmvae_decoder_recon_wplanes_f32; taken together with h_planes)
-        if dP_planes is not None:
-            raise ValueError("decoder_recon: W_planes and dP_planes have no common entry point")
-        hp, wp = h_planes, W_planes
-        rc = lib.mmvae_decoder_recon_wplanes_f32(
-            R, B, G, H, _ptr(h), ldh, hp.ptr() if hp else None, hp.ld if hp else 0, hp.plane_stride if hp else 0,
-            _ptr(W), ldw, wp.ptr(), wp.ld, wp.plane_stride, _ptr(bias), _ptr(x), ldx, _ptr(xhat), ldxh, _ptr(dP), lddp,
-            _ptr(se_part), _ptr(col_part), _stream(),
-        )
-        _lib.check(rc, "mmvae_decoder_recon_wplanes_f32")
-        return xhat, dP, se_part
-    if h_planes is not None or dP_planes is not None:
-        hp, dpp = h_planes, dP_planes
-        rc = lib.mmvae_decoder_recon_planes_f32(
-            R, B, G, H, _ptr(h), ldh, hp.ptr() if hp else None, hp.ld if hp else 0, hp.plane_stride if hp else 0,
-            _ptr(W), ldw, _ptr(bias), _ptr(x), ldx, _ptr(xhat), ldxh, _ptr(dP), lddp,
-            dpp.ptr() if dpp else None, dpp.ld if dpp else 0, dpp.plane_stride if dpp else 0,
-            _ptr(se_part), _ptr(col_part), _stream(),
-        )
-        _lib.check(rc, "mmvae_decoder_recon_planes_f32")
-        return xhat, dP, se_part
+    if W_planes is not None and dP_planes is not None:
+        raise ValueError("decoder_recon: W_planes together with dP_planes is refused (no kernel takes both)")
     if h_kpad and ldh < (H + 31) // 32 * 32:
         raise ValueError("decoder_recon: h_kpad needs h's leading dimension to cover the padded width")
-    lib.mmvae_recon_set_h_kpad(1 if h_kpad else 0)
-    try:
-        rc = lib.mmvae_decoder_recon_rows_colsum_f32(
-            R, B, G, H, _ptr(h), ldh, _ptr(W), ldw, _ptr(bias), _ptr(x), ldx, _ptr(xhat), ldxh, _ptr(dP), lddp,
-            _ptr(se_part), _ptr(col_part), _stream(),
-        )
-    finally:
-        lib.mmvae_recon_set_h_kpad(0)
-    _lib.check(rc, "mmvae_decoder_recon_rows_colsum_f32")
+    args = _lib.ReconArgs(
+        rows=R, x_rows=B, G=G, H=H, flags=_lib.RECON_H_KPAD if h_kpad else 0, h=_ptr(h), W=_ptr(W), bias=_ptr(bias),
+        x=_ptr(x), ldh=ldh, ldw=ldw, ldx=ldx, xhat=_ptr(xhat), dP=_ptr(dP), se_part=_ptr(se_part),
+        col_part=_ptr(col_part), ldxhat=ldxh, lddp=lddp, h_planes=_c_planes(h_planes), W_planes=_c_planes(W_planes),
+        dP_planes=_c_planes(dP_planes))
+    _lib.check(lib.mmvae_decoder_recon(args, _stream()), "mmvae_decoder_recon")
     return xhat, dP, se_part
 
 
@@ -377,7 +365,7 @@ def fc_epilogue_fwd(
     rc = lib.mmvae_fc_epilogue_fwd(
         B, N, _ptr(inp), N, S, _ptr(bias), C.byref(bnp) if bnp is not None else None, int(training), int(relu),
         _ptr(keep_mask), float(dropout_p), _ptr(z), _ptr(a), _ptr(d), N, _ptr(mean), _ptr(invstd), _ptr(ws), nws,
-        _stream(),
+        None, None, _stream(),
     )
     _lib.check(rc, "mmvae_fc_epilogue_fwd")
     return {"z": z, "a": a if a is not None else d, "d": d, "mean": mean, "invstd": invstd}
@@ -430,7 +418,7 @@ def fc_epilogue_bwd(
     rc = lib.mmvae_fc_epilogue_bwd(
         B, N, _ptr(din), N, S, _ptr(addend), _ptr(addend_a), _ptr(row_scale), _ptr(keep_mask), float(dropout_p), int(relu), _ptr(a),
         _ptr(z), _ptr(gamma), _ptr(mean), _ptr(invstd), int(has_bn), _ptr(dz), N, _ptr(dbias), _ptr(dgamma),
-        _ptr(dbeta), _ptr(ws), nws, _stream(),
+        _ptr(dbeta), _ptr(ws), nws, None, _stream(),
     )
     _lib.check(rc, "mmvae_fc_epilogue_bwd")
     return dz, dbias, dgamma, dbeta

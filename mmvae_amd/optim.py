@@ -67,7 +67,7 @@ class ParamArena:
         self.numel = n
         # 32 spare elements behind each arena: its tensors may be read as rows-contiguous GEMM operands in 16-byte groups
         # up to 12 bytes past their end (MMVAE_GEMM_OPERAND_SLACK), a weight matrix row up to the next multiple of 32
-        # columns (mmvae_recon_set_h_kpad)
+        # columns (MMVAE_RECON_H_KPAD)
         # (the padded tensors themselves: a sharded exchange works on the arena rounded up to 4 x world elements)
         self.data_full = torch.zeros(n + 32, dtype=torch.float32, device=dev)
         self.grad_full = torch.zeros(n + 32, dtype=torch.float32, device=dev)

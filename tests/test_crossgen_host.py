@@ -38,12 +38,13 @@ def test_header_declares_and_lib_binds_the_correlation_entry_points():
         assert chunks * ((G + 255) // 256) >= 512
 
 
-def test_abi_version_is_15():
+def test_abi_version_is_16():
+    """15 added the per-gene correlation entries; 16 folded the reconstruction / FC-epilogue entry-point ladders."""
     from mmvae_amd import _lib
 
     header = open(os.path.join(ROOT, "include", "mmvae_hip.h")).read()
-    assert int(re.search(r"#define\s+MMVAE_ABI_VERSION\s+(\d+)", header).group(1)) == 15
-    assert _lib.load().mmvae_abi_version() == 15
+    assert int(re.search(r"#define\s+MMVAE_ABI_VERSION\s+(\d+)", header).group(1)) == 16
+    assert _lib.load().mmvae_abi_version() == 16
 
 
 def test_generate_layout_stays_on_one_stream():

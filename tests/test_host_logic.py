@@ -186,6 +186,92 @@ def test_abi_header_symbols_are_exported_and_bound():
     assert lib.mmvae_gemm_set_precision(_lib.GEMM_PRECISION_BF16X3) == 0
 
 
+def test_abi_structs_have_the_librarys_layout_and_nothing_undeclared_is_exported():
+    import ctypes
+    from mmvae_amd import _lib
+
+    lib = _lib.load()
+    assert ctypes.sizeof(_lib.Planes) == lib.mmvae_sizeof_planes() == 24
+    assert ctypes.sizeof(_lib.ReconArgs) == lib.mmvae_sizeof_recon_args()
+    assert ctypes.sizeof(_lib.SplitJob) == lib.mmvae_sizeof_split_job()
+    # a retired entry point is gone from the library too: it exports no mmvae_* symbol that the header does not declare
+    # (candidates: every such name in the file's string tables; exported: the loader resolves it)
+    header = open(os.path.join(ROOT, "include", "mmvae_hip.h")).read()
+    declared = set(re.findall(r"\b(mmvae_[a-z0-9_]+)\s*\(", header))
+    image = open(_lib.LIB_PATH, "rb").read()
+    names = {m.decode() for m in re.findall(rb"(?<![A-Za-z0-9_])mmvae_[a-z0-9_]+(?=\x00)", image)}
+    assert declared - {"mmvae_bn_params"} <= names, "the scan of the string tables misses exported names"
+    stale = sorted(n for n in names - declared if hasattr(lib, n))
+    assert not stale, f"exported but not declared in the header: {stale}"
+
+
+def _host_block():
+    """(keep-alive, address): 16-byte aligned host memory standing in for device buffers in calls that must be refused
+    before anything is launched"""
+    import ctypes
+
+    buf = ctypes.create_string_buffer(4096 + 16)
+    return buf, (ctypes.addressof(buf) + 15) // 16 * 16
+
+
+def test_decoder_recon_refuses_bad_arguments_on_the_host():
+    """One case per validation of mmvae_decoder_recon: every one returns MMVAE_ERR_ARG before any HIP call (no GPU here)."""
+    from mmvae_amd import _lib
+
+    lib = _lib.load()
+    keep, p = _host_block()
+    planes = _lib.Planes(p, 64, 64 * 64)
+
+    def call(**kw):
+        a = dict(rows=64, x_rows=32, G=64, H=32, h=p, W=p, bias=p, x=p, ldh=32, ldw=32, ldx=64, xhat=p, dP=p, se_part=p,
+                 col_part=p, ldxhat=64, lddp=64)
+        a.update(kw)
+        return lib.mmvae_decoder_recon(_lib.ReconArgs(**a), None)
+
+    assert lib.mmvae_decoder_recon(None, None) == _lib.ERR_ARG                      # NULL args
+    assert call(flags=2) == _lib.ERR_ARG and call(flags=_lib.RECON_H_KPAD | 4) == _lib.ERR_ARG  # unknown flag bits
+    assert call(rows=65) == _lib.ERR_ARG                                            # rows % x_rows != 0
+    assert call(rows=0) == _lib.ERR_ARG and call(G=0) == _lib.ERR_ARG and call(H=0) == _lib.ERR_ARG
+    assert call(h=None) == _lib.ERR_ARG and call(W=None) == _lib.ERR_ARG and call(x=None) == _lib.ERR_ARG
+    assert call(se_part=None) == _lib.ERR_ARG                                       # missing se_part
+    assert call(ldh=31) == _lib.ERR_ARG and call(ldw=31) == _lib.ERR_ARG and call(ldx=63) == _lib.ERR_ARG
+    assert call(ldxhat=63) == _lib.ERR_ARG and call(lddp=63) == _lib.ERR_ARG
+    # planes of dP: the shape rules, and bf16x3 precision only
+    assert call(dP_planes=_lib.Planes(p, 60, 64 * 64)) == _lib.ERR_ARG             # ld < G / not a multiple of 8
+    assert call(dP_planes=_lib.Planes(p, 64, 63 * 64)) == _lib.ERR_ARG             # plane stride < rows * ld
+    assert call(dP_planes=_lib.Planes(p + 2, 64, 64 * 64)) == _lib.ERR_ARG         # base not 16-byte aligned
+    assert lib.mmvae_gemm_set_precision(_lib.GEMM_PRECISION_F32) == 0
+    try:
+        assert call(dP_planes=planes) == _lib.ERR_ARG                               # dP_planes under exact-f32 precision
+    finally:
+        assert lib.mmvae_gemm_set_precision(_lib.GEMM_PRECISION_BF16X3) == 0
+    # never launched together before this entry point existed: refused, not enabled
+    assert call(W_planes=planes, dP_planes=planes) == _lib.ERR_ARG
+    assert call(h_planes=planes, W_planes=planes, dP_planes=planes) == _lib.ERR_ARG
+    # planes of h that cannot be used (a leading dimension off a multiple of 8) and no fp32 h to fall back to
+    assert call(h=None, h_planes=_lib.Planes(p, 36, 64 * 36)) == _lib.ERR_ARG
+    del keep
+
+
+def test_fc_epilogue_fwd_refuses_planes_with_split_and_a_split_without_planes():
+    from mmvae_amd import _lib
+
+    lib = _lib.load()
+    keep, p = _host_block()
+    B, N = 32, 64
+    planes = _lib.Planes(p, N, B * N)
+
+    def call(d_planes, split):
+        return lib.mmvae_fc_epilogue_fwd(B, N, p, N, 1, p, None, 1, 1, None, 0.0, None, None, p, N, None, None, None, 0,
+                                         d_planes, split, None)
+
+    assert call(planes, _lib.SplitJob(B, N, p, N, planes)) == _lib.ERR_ARG         # never launched together: refused
+    assert call(None, _lib.SplitJob(B, N, p, N, _lib.Planes())) == _lib.ERR_ARG    # a split job without planes
+    assert call(None, _lib.SplitJob(B, N, p, N, _lib.Planes(p, N - 8, B * N))) == _lib.ERR_ARG   # ... whose ld < cols
+    assert call(_lib.Planes(p, N - 2, B * N), None) == _lib.ERR_ARG                # output planes with ld < N
+    del keep
+
+
 def test_product_package_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "mmvae_amd")
     for dp, _, files in os.walk(pkg):

@@ -216,7 +216,7 @@ def test_decoder_recon(ops, R, B, G, H):
 
 @pytest.mark.parametrize("R,B,G,H", [(512, 512, 20000, 1000), (512, 512, 20000, 1016), (256, 128, 5008, 72)])
 def test_decoder_recon_hidden_width_off_the_k_tile(ops, R, B, G, H):
-    """A hidden width that is not a multiple of 32 on the pipelined kernels (mmvae_recon_set_h_kpad): h in a buffer padded
+    """A hidden width that is not a multiple of 32 on the pipelined kernels (MMVAE_RECON_H_KPAD): h in a buffer padded
     with zero columns, W's rows read on into the next row (the last one into readable slack) -- same results as the
     guarded loop (to rounding) and as fp64."""
     h, bias = rnd(R, H, seed=1), rnd(G, seed=3, scale=0.1)
@@ -240,6 +240,29 @@ def test_decoder_recon_hidden_width_off_the_k_tile(ops, R, B, G, H):
     assert rel_l2(col_part.sum(0), dP.double().sum(0)) < 1e-6
     xhat_g, _, se_g = ops.decoder_recon(dev(h), Wd, dev(bias), dev(x))  # the guarded loop
     assert rel_l2(xhat, xhat_g) < 2e-6 and rel_l2(se_part.sum(0), se_g.sum(0)) < 1e-5
+
+
+def test_decoder_recon_k_padding_promise_is_per_call(ops):
+    """MMVAE_RECON_H_KPAD vouches for ONE launch's buffers: a launch without the flag on an unpadded h, straight after a
+    flagged launch on a padded one, takes the guarded loop again -- bit-identical to such a launch made before."""
+    R, B, G, H = 256, 128, 5008, 72  # hidden width off the 32-wide k-tile, gene count off the tile width
+    h, bias, x = dev(rnd(R, H, seed=1)), dev(rnd(G, seed=3, scale=0.1)), dev(rnd(B, G, seed=4).abs())
+    hpad = torch.zeros(R, (H + 31) // 32 * 32, device="cuda")
+    hpad[:, :H] = h
+    Wbuf = torch.zeros(G * H + 32, device="cuda")  # (32 readable floats behind the last row, as the flag asks)
+    Wbuf[:G * H] = dev(rnd(G, H, seed=2, scale=0.2)).reshape(-1)
+    Wd = Wbuf[:G * H].view(G, H)
+
+    def guarded():
+        col_part = torch.zeros(ops.recon_row_tiles(R), G, device="cuda")
+        return (*ops.decoder_recon(h, Wd, bias, x, col_part=col_part), col_part)
+
+    before = guarded()
+    xhat, _, se_part = ops.decoder_recon(hpad[:, :H], Wd, bias, x, h_kpad=True)
+    after = guarded()
+    for name, b, a in zip(("xhat", "dP", "se_part", "col_part"), before, after):
+        assert torch.equal(b, a), name
+    assert rel_l2(xhat, before[0]) < 2e-6 and rel_l2(se_part.sum(0), before[2].sum(0)) < 1e-5
 
 
 # --------------------------------------------------------------------------------------------------- FC epilogues
@@ -781,8 +804,8 @@ def test_csr_spmm_against_dense(ops, B, G, N, density):
 @pytest.mark.parametrize("layout,M,N,K", [(2, 1024, 20000, 64), (2, 20000, 1024, 32), (0, 512, 20000, 96),
                                            (2, 2048, 2004, 40), (1, 640, 20000, 64)])
 def test_gemm_with_fused_sum_of_squares(ops, layout, M, N, K):
-    """mmvae_gemm_f32_sq: same product as mmvae_gemm_f32 (bitwise) plus per-tile partial sums of squares of the stored
-    values whose total is the squared Frobenius norm (rtol 1e-5: fp32 partials, any tile shape the planner picks)."""
+    """mmvae_gemm_planes_f32 with sq_partials: same product as mmvae_gemm_f32 (bitwise) plus per-tile partial sums of
+    squares of the stored values whose total is the squared Frobenius norm (rtol 1e-5: fp32 partials, any tile shape the planner picks)."""
     a, b = rnd(M, K, seed=11), rnd(K, N, seed=12)
     A = a if layout != 2 else a.t().contiguous()
     Bm = b.t().contiguous() if layout == 0 else b

@@ -149,7 +149,8 @@ def _bn(N):
 
 @pytest.mark.parametrize("B,N,S", [(512, 1024, 4), (100, 256, 1), (33, 64, 2)])
 def test_layer_tails_write_planes(ops, B, N, S):
-    """mmvae_fc_epilogue_fwd_planes / _bwd_planes: the planes are exactly the fp32 outputs of the plain entry points."""
+    """mmvae_fc_epilogue_fwd / _bwd with d_planes / dz_planes: the planes are exactly the fp32 outputs of the launches
+    without them."""
     import ctypes as C
 
     from mmvae_amd import _lib
@@ -161,8 +162,8 @@ def test_layer_tails_write_planes(ops, B, N, S):
     d = torch.empty(B, N, device="cuda")
     pl = ops.Planes(B, N, "cuda")
     st = torch.cuda.current_stream().cuda_stream
-    rc = lib.mmvae_fc_epilogue_fwd_planes(B, N, slabs.data_ptr(), N, S, bias.data_ptr(), None, 1, 1, None, 0.0, None, None,
-                                          d.data_ptr(), N, None, None, None, 0, pl.ptr(), pl.ld, pl.plane_stride, st)
+    rc = lib.mmvae_fc_epilogue_fwd(B, N, slabs.data_ptr(), N, S, bias.data_ptr(), None, 1, 1, None, 0.0, None, None,
+                                   d.data_ptr(), N, None, None, None, 0, pl.as_c(), None, st)
     assert rc == 0
     assert torch.equal(d, ref["d"]) and torch.equal(pl.to_float(), d)
     # backward through a BatchNorm layer: the final dz and its planes
@@ -177,18 +178,15 @@ def test_layer_tails_write_planes(ops, B, N, S):
         args = (B, N, slabs.data_ptr(), N, S, None, None, None, None, 0.0, 1, a_act.data_ptr(), z.data_ptr(),
                 gamma.data_ptr(), mean.data_ptr(), invstd.data_ptr(), 1, dz.data_ptr(), N, None, None, None,
                 ws.data_ptr(), ws.numel() * 4)
-        if planes is None:
-            rc = lib.mmvae_fc_epilogue_bwd(*args, st)
-        else:
-            rc = lib.mmvae_fc_epilogue_bwd_planes(*args, planes.ptr(), planes.ld, planes.plane_stride, st)
+        rc = lib.mmvae_fc_epilogue_bwd(*args, None if planes is None else planes.as_c(), st)
         assert rc == 0
         outs.append((dz, planes))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[1][1].to_float(), outs[1][0])
 
 
 def test_layer_tail_with_piggybacked_split(ops):
-    """mmvae_fc_epilogue_fwd_split: the tail's own outputs are unchanged and the extra workgroups split a row range of an
-    unrelated matrix (the engine's input batch, a third of the rows per tail)."""
+    """mmvae_fc_epilogue_fwd with a split job: the tail's own outputs are unchanged and the extra workgroups split a row
+    range of an unrelated matrix (the engine's input batch, a third of the rows per tail)."""
     from mmvae_amd import _lib
 
     lib = _lib.load()
@@ -208,11 +206,12 @@ def test_layer_tail_with_piggybacked_split(ops):
     import ctypes as C
 
     r0, nrows = 171, 171  # the middle third
-    rc = lib.mmvae_fc_epilogue_fwd_split(B, N, slabs.data_ptr(), N, S, bias.data_ptr(), C.byref(bnp), 1, 1, mask.data_ptr(),
-                                         0.1, z.data_ptr(), a.data_ptr(), d.data_ptr(), N, mean.data_ptr(),
-                                         invstd.data_ptr(), ws.data_ptr(), ws.numel() * 4, nrows, G,
-                                         x.data_ptr() + 4 * r0 * G, G, xp.ptr() + 2 * r0 * xp.ld, xp.ld, xp.plane_stride,
-                                         torch.cuda.current_stream().cuda_stream)
+    job = _lib.SplitJob(nrows, G, x.data_ptr() + 4 * r0 * G, G,
+                        _lib.Planes(xp.ptr() + 2 * r0 * xp.ld, xp.ld, xp.plane_stride))
+    rc = lib.mmvae_fc_epilogue_fwd(B, N, slabs.data_ptr(), N, S, bias.data_ptr(), C.byref(bnp), 1, 1, mask.data_ptr(),
+                                   0.1, z.data_ptr(), a.data_ptr(), d.data_ptr(), N, mean.data_ptr(),
+                                   invstd.data_ptr(), ws.data_ptr(), ws.numel() * 4, None, job,
+                                   torch.cuda.current_stream().cuda_stream)
     assert rc == 0
     for k, t in (("z", z), ("a", a), ("d", d), ("mean", mean), ("invstd", invstd)):
         assert torch.equal(t, ref[k]), k
@@ -227,10 +226,11 @@ def test_layer_tail_with_piggybacked_split(ops):
     tiny[::3, ::5] = rnd(B, G, seed=23)[::3, ::5]  # ordinary neighbours beside the tiny ones
     want = ops.split_planes(tiny)
     xp2 = ops.Planes(B, G, "cuda")
-    rc = lib.mmvae_fc_epilogue_fwd_split(B, N, slabs.data_ptr(), N, S, bias.data_ptr(), C.byref(bnp), 1, 1, mask.data_ptr(),
-                                         0.1, z.data_ptr(), a.data_ptr(), d.data_ptr(), N, mean.data_ptr(),
-                                         invstd.data_ptr(), ws.data_ptr(), ws.numel() * 4, B, G, tiny.data_ptr(), G,
-                                         xp2.ptr(), xp2.ld, xp2.plane_stride, torch.cuda.current_stream().cuda_stream)
+    job = _lib.SplitJob(B, G, tiny.data_ptr(), G, xp2.as_c())
+    rc = lib.mmvae_fc_epilogue_fwd(B, N, slabs.data_ptr(), N, S, bias.data_ptr(), C.byref(bnp), 1, 1, mask.data_ptr(),
+                                   0.1, z.data_ptr(), a.data_ptr(), d.data_ptr(), N, mean.data_ptr(),
+                                   invstd.data_ptr(), ws.data_ptr(), ws.numel() * 4, None, job,
+                                   torch.cuda.current_stream().cuda_stream)
     assert rc == 0
     assert torch.equal(xp2.data[:, :B], want.data[:, :B])
 

@@ -7,6 +7,8 @@ import sys
 
 import torch
 
+from mmvae_amd._lib import ReconArgs  # (the struct only: both libraries are loaded by path below)
+
 libs = [C.CDLL(p) for p in sys.argv[1:3]]
 rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 7
 B, G, H1 = 512, 20000, 1024
@@ -21,6 +23,8 @@ sep = torch.empty(256 * B, device=dev)
 p = lambda t: C.c_void_p(t.data_ptr())
 f, i64, i32, u32, z = C.c_float, C.c_int64, C.c_int, C.c_uint, C.c_size_t
 S = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+recon_args = ReconArgs(rows=B, x_rows=B, G=G, H=H1, h=h.data_ptr(), ldh=H1, W=W4.data_ptr(), ldw=H1, bias=b4.data_ptr(),
+                       x=x.data_ptr(), ldx=G, dP=out_big.data_ptr(), lddp=G, se_part=sep.data_ptr())
 
 
 def gemm(lib, layout, M, N, K, A, lda, Bm, ldb, Cm, ldc, flags, sk):
@@ -32,9 +36,7 @@ def gemm(lib, layout, M, N, K, A, lda, Bm, ldb, Cm, ldc, flags, sk):
 cases = {
     "k1 enc-L1 fwd NT slabs x16": lambda lib: gemm(lib, 0, B, H1, G, x, G, W1, G, ws, H1, 4, 16),
     "k2 enc-L1 dW  TN 1024x20000x512": lambda lib: gemm(lib, 2, H1, G, B, dY1, H1, x, G, out_big, G, 0, 1),
-    "k3 dec-L2 fwd+recon NT": lambda lib: lib.mmvae_decoder_recon_rows_f32(
-        i32(B), i32(B), i32(G), i32(H1), p(h), i64(H1), p(W4), i64(H1), p(b4), p(x), i64(G), None, i64(0), p(out_big),
-        i64(G), p(sep), S()),
+    "k3 dec-L2 fwd+recon NT": lambda lib: lib.mmvae_decoder_recon(C.byref(recon_args), S()),
     "k4a dec-L2 dW TN 20000x1024x512": lambda lib: gemm(lib, 2, G, H1, B, dP, G, h, H1, out_big, H1, 0, 1),
     "k4b dec-L2 dX NN slabs x16": lambda lib: gemm(lib, 1, B, H1, G, dP, G, W4, H1, ws, H1, 4, 16),
 }
