@@ -273,3 +273,39 @@ def col_pearson(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     r = (da * db).sum(0) / torch.sqrt((da * da).sum(0) * (db * db).sum(0))
     constant = (a == a[0]).all(0) | (b == b[0]).all(0)
     return torch.where(constant, torch.full_like(r, float("nan")), r.clamp(-1.0, 1.0)).float()
+
+
+def row_corrcoef(a: torch.Tensor, b: Optional[torch.Tensor] = None, *, want_matrix: bool = True):
+    """(corr, stats) of the ROWS of the stacked [n_a + n_b, genes] matrix (a ; b) -- `np.corrcoef` of a cis generation
+    stacked on a cross generation and the block means calc_correlations (runners/run_correlations.py:18-60) reports.
+    corr [R, R]: clamped to [-1, 1], NaN in the row and column of every constant row (numpy's 0 / 0), 1 on the rest of
+    the diagonal.  stats float64[8]: the nan_to_num means of corr[:n_a, :n_a] (cis), corr[n_a:, n_a:] (cross) and
+    corr[:n_a, n_a:] (comb), 2 comb / (cis + cross), the constant-row counts of a and of b, 0, 0; NaN for the three
+    statistics that need b when there is none.  Device tensors: the HIP kernels of libmmvae_stats.so
+    (ops.row_corrcoef; corr fp32, nothing is stacked).  CPU tensors only under backend.cpu_plumbing(): the centred
+    statement in fp64, corr returned as fp64 (host-logic tests).  want_matrix=False: corr is None (on the device it is
+    then never stored)."""
+    from . import backend
+
+    if backend.on_hip(a):
+        return ops.row_corrcoef(a, b, want_matrix=want_matrix)
+    n_a = a.shape[0]
+    x = a.double() if b is None else torch.cat([a.double(), b.double()], 0)
+    n_b = x.shape[0] - n_a
+    d = x - x.mean(1, keepdim=True)
+    cov = d @ d.T
+    var = cov.diagonal()
+    corr = (cov / torch.sqrt(var[:, None] * var[None, :])).clamp(-1.0, 1.0)
+    corr.fill_diagonal_(1.0)
+    constant = (x == x[:, :1]).all(1)
+    corr[constant, :] = float("nan")
+    corr[:, constant] = float("nan")
+    z = torch.nan_to_num(corr, nan=0.0)
+    nan = torch.tensor(float("nan"), dtype=torch.float64)
+    cis = z[:n_a, :n_a].mean()
+    cross = z[n_a:, n_a:].mean() if n_b else nan
+    comb = z[:n_a, n_a:].mean() if n_b else nan
+    stats = torch.zeros(8, dtype=torch.float64)
+    stats[0], stats[1], stats[2], stats[3] = cis, cross, comb, 2.0 * comb / (cis + cross)
+    stats[4], stats[5] = constant[:n_a].sum(), constant[n_a:].sum()
+    return (corr if want_matrix else None), stats

@@ -323,6 +323,50 @@ class CMMVAEModel(BaseModel):
         r = HF.col_pearson(a, b)
         return r, torch.nanmean(r), (~torch.isnan(r)).sum()
 
+    @staticmethod
+    def cell_correlation(cis: torch.Tensor, cross: torch.Tensor, decimals: Optional[int] = 3) -> dict:
+        """The statistics calc_correlations (runners/run_correlations.py:18-60) reports for one species: `cis` [n, genes]
+        is its own generation, `cross` [m, genes] the other species' cells generated through its expert.  Over
+        C = corrcoef of the rows of the stacked matrix (HF.row_corrcoef: HIP kernels on device tensors, nothing is
+        stacked or moved to the host but eight numbers): "cis", "cross", "comb" = the nan_to_num means of C[:n, :n],
+        C[n:, n:], C[:n, n:], rounded as np.round rounds the fp64 value; "rel" = round(2 comb / (cis + cross)) computed
+        from the ROUNDED means, as the reference does; "n_constant" = the number of constant rows (NaN in C, counted as
+        0 by the means).  decimals=None: the unrounded means and the unrounded rel of the unrounded means."""
+        import numpy as np
+
+        _, stats = HF.row_corrcoef(cis, cross, want_matrix=False)
+        s = stats.cpu().numpy()
+        cis_m, cross_m, comb_m, rel = s[0], s[1], s[2], s[3]
+        if decimals is not None:
+            cis_m, cross_m, comb_m = (np.round(v, decimals) for v in (cis_m, cross_m, comb_m))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                rel = np.round((2 * comb_m) / (cis_m + cross_m), decimals)
+        return {"cis": float(cis_m), "cross": float(cross_m), "comb": float(comb_m), "rel": float(rel),
+                "n_constant": int(s[4] + s[5])}
+
+    @torch.no_grad()
+    def cross_species_correlation(self, batch_a, batch_b, decimals: Optional[int] = 3) -> dict:
+        """One row of get_correlations (runners/run_correlations.py:95-145): both batches -- `(x, metadata, expert_id)` of
+        two different experts -- go through cross_generate_step to both experts, and for each expert `s`
+        cell_correlation is applied to (the `s -> s` rows, the `other -> s` rows).  Keys: f"{id}_cis", f"{id}_cross",
+        f"{id}_comb", f"{id}_rel" for batch_a's expert, then for batch_b's.
+        The reference slices BOTH stacked matrices at the human sample count (run_correlations.py:119,133), which is
+        right only while the two groups hold the same number of cells; here every stacked matrix is split at its own
+        cis row count."""
+        id_a, id_b = batch_a[2], batch_b[2]
+        if id_a == id_b:
+            raise ValueError(f"cross_species_correlation: both batches belong to expert {id_a!r}")
+        # (cross_generate_step hands out clones of the engine's xhat buffers, so the first call's survive the second)
+        out_a = self.cross_generate_step(batch_a, targets=[id_a, id_b])
+        from_a = {s: out_a[f"xhat_{s}"][0] for s in (id_a, id_b)}
+        out_b = self.cross_generate_step(batch_b, targets=[id_a, id_b])
+        from_b = {s: out_b[f"xhat_{s}"][0] for s in (id_a, id_b)}
+        row = {}
+        for s, cis, cross in ((id_a, from_a[id_a], from_b[id_a]), (id_b, from_b[id_b], from_a[id_b])):
+            c = self.cell_correlation(cis, cross, decimals=decimals)
+            row.update({f"{s}_{k}": c[k] for k in ("cis", "cross", "comb", "rel")})
+        return row
+
     # -------------------------------------------------------------------------------------------------- optimisers
     def get_optimizers(self, zero_all: bool = False):
         """The optimisers in the shape of `optimizer_map`: {"experts": {id: opt}, "vae": opt, "adversarials": {n: opt}}

@@ -951,3 +951,46 @@ def col_pearson(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = 
     _lib.check(lib.mmvae_col_pearson_f32(B, G, _ptr(a), lda, _ptr(b), ldb, _ptr(out), _ptr(ws), nbytes, _stream()),
                "mmvae_col_pearson_f32")
     return out
+
+
+def row_corrcoef(a: torch.Tensor, b: Optional[torch.Tensor] = None, *, want_matrix: bool = True,
+                 out: Optional[torch.Tensor] = None):
+    """(corr, stats) of the rows of the stacked matrix (a ; b), which is never formed (mmvae_stats_row_corr_f32 of
+    libmmvae_stats.so).  `a` [n_a, G] and `b` [n_b, G] (or None): fp32 row-major views with any row stride, 2 <= n_a +
+    n_b <= 2048, G >= 2.  corr [R, R] fp32 is np.corrcoef of the rows, clamped to [-1, 1], bitwise symmetric, NaN in
+    the row and column of every constant row and exactly 1 on the rest of the diagonal; None with want_matrix=False.
+    stats: device float64[8] = the nan_to_num means of corr[:n_a, :n_a] (cis), corr[n_a:, n_a:] (cross), corr[:n_a,
+    n_a:] (comb), 2 comb / (cis + cross), the constant-row counts of a and of b, 0, 0.  `out`: an [R, R] fp32 view to
+    write corr into (inner stride 1)."""
+    from . import _stats_lib
+
+    lib = _stats_lib.load_stats()
+    _chk(a, "a"), _chk(b, "b"), _chk(out, "out")
+    n_a, G, lda = _mat(a, "a")
+    n_b, ldb = 0, 0
+    if b is not None:
+        n_b, Gb, ldb = _mat(b, "b")
+        if Gb != G:
+            raise ValueError(f"row_corrcoef: a {tuple(a.shape)} vs b {tuple(b.shape)}")
+        if b.device != a.device:
+            raise ValueError(f"row_corrcoef: a and b must be on one device (a on {a.device}, b on {b.device})")
+        if n_b == 0:
+            b = None
+    R = n_a + n_b
+    corr, ldc = None, 0
+    if out is not None:
+        if not want_matrix:
+            raise ValueError("row_corrcoef: out given with want_matrix=False")
+        Ro, Co, ldc = _mat(out, "out")
+        if (Ro, Co) != (R, R) or out.device != a.device:
+            raise ValueError(f"row_corrcoef: out must be a [{R}, {R}] tensor on {a.device}")
+        corr = out
+    elif want_matrix:
+        corr = torch.empty((R, R), dtype=torch.float32, device=a.device)
+        ldc = R
+    stats = torch.empty((_stats_lib.ROW_CORR_STATS,), dtype=torch.float64, device=a.device)
+    nbytes = lib.mmvae_stats_row_corr_workspace_bytes(n_a, n_b, G)
+    ws = workspace(nbytes, a.device, kind="row_corr")
+    _lib.check(lib.mmvae_stats_row_corr_f32(n_a, n_b, G, _ptr(a), lda, _ptr(b), ldb, _ptr(corr), ldc, _ptr(stats),
+                                            _ptr(ws), nbytes, _stream()), "mmvae_stats_row_corr_f32")
+    return corr, stats

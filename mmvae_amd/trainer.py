@@ -163,3 +163,25 @@ class Trainer:
             writer.write_on_batch_end(self, model, model.cross_generate_step(batch, i, targets=targets), None, batch, i, 0)
         writer.on_predict_epoch_end(self, model)
         return []
+
+    @torch.no_grad()
+    def correlations(self, model, groups: Iterable, decimals: Optional[int] = 3):
+        """The table of get_correlations (runners/run_correlations.py:95-145) as a pandas.DataFrame, one row per group of
+        `groups` = (group_id, batch_a, batch_b) with the two batches of different experts
+        (`CMMVAEModel.cross_species_correlation`): "group_id", "num_samples" (the cells of batch_a), the eight
+        statistic columns, and whichever of RK.FILTER_CATEGORIES batch_a's metadata holds (its first row), sorted by
+        group_id as save_correlations does.  Writing the CSV, the pickle and the plot is left to the caller."""
+        import pandas as pd
+
+        from .constants import REGISTRY_KEYS as RK
+
+        model.eval()
+        model.trainer.set_stage("prediction")
+        rows = []
+        for group_id, batch_a, batch_b in groups:
+            stats = model.cross_species_correlation(batch_a, batch_b, decimals=decimals)
+            metadata = batch_a[1]
+            cats = {c: metadata[c].iloc[0] for c in RK.FILTER_CATEGORIES if c in metadata.columns}
+            rows.append({"group_id": group_id, "num_samples": int(batch_a[0].shape[0]), **stats, **cats})
+        table = pd.DataFrame(rows)
+        return table.sort_values("group_id").reset_index(drop=True) if rows else table

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Cross-generation and the per-gene correlation behind it, measured.
+"""Cross-generation and the statistics computed on it, measured.
 
-Three legs, each in a child process of its own under its own time limit (a leg that faults, aborts or runs out of time
+Four legs, each in a child process of its own under its own time limit (a leg that faults, aborts or runs out of time
 ends the run: nothing more is started on the device):
 
   step-c2    ms per CMMVAEModel.cross_generate_step to ALL experts, captured engine against the module path, interleaved
@@ -10,6 +10,9 @@ ends the run: nothing more is started on the device):
   pearson    us of mmvae_col_pearson_f32 at (100, 60 530), (512, 20 000), (512, 60 530) with the achieved GB/s against
              the bytes of both matrices, and us of the torch statement of the same statistic (centre, multiply, sum; no
              torch.corrcoef) on the same inputs
+  cellcorr   us of mmvae_stats_row_corr_f32 (cell-by-cell correlation of a cis on a cross generation and its block
+             means) at (100 + 100, 20 000), (100 + 100, 60 530), (512 + 512, 20 000), and of torch.corrcoef on the device
+             in fp32 and in fp64 on the stacked copy, the copy's time listed separately
 
 Nothing is asserted: the numbers are reported.  Output: the lines below, also written to --out (default
 profiles/crossgen.txt)."""
@@ -24,7 +27,8 @@ sys.path.insert(0, ROOT)
 
 GENES = {"c2": {"human": 20000, "mouse": 20000}, "full": {"human": 60530, "mouse": 52437}}
 PEARSON_SHAPES = [(100, 60530), (512, 20000), (512, 60530)]
-LEGS = {"step-c2": 240, "step-full": 300, "pearson": 240}  # seconds
+CELLCORR_SHAPES = [(100, 100, 20000), (100, 100, 60530), (512, 512, 20000)]
+LEGS = {"step-c2": 240, "step-full": 300, "pearson": 240, "cellcorr": 240}  # seconds
 
 
 def leg_step(which: str, blocks: int, steps: int):
@@ -66,6 +70,21 @@ def leg_step(which: str, blocks: int, steps: int):
     print(f"  module / engine : {med(mod) / med(eng):8.2f} x")
 
 
+def timed(fn, n):
+    import torch
+
+    for _ in range(5):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n * 1e3
+
+
 def leg_pearson(reps: int):
     import torch
 
@@ -74,18 +93,6 @@ def leg_pearson(reps: int):
     def torch_statement(a, b):
         da, db = a - a.mean(0), b - b.mean(0)
         return (da * db).sum(0) / torch.sqrt((da * da).sum(0) * (db * db).sum(0))
-
-    def timed(fn, n):
-        for _ in range(5):
-            fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n * 1e3
 
     print(f"per-gene Pearson correlation, {reps} back-to-back calls each (device events; two launches per HIP call); "
           "GB/s = bytes of both matrices / time:")
@@ -110,6 +117,43 @@ def leg_pearson(reps: int):
             print(f"    {name:<52s} {us:9.1f} us   {nbytes / us / 1e3:8.1f} GB/s")
 
 
+def leg_cellcorr(reps: int):
+    import torch
+
+    from mmvae_amd import ops, synthetic
+
+    print(f"cell-by-cell correlation of (cis ; cross), {reps} back-to-back calls each (device events; four launches per "
+          "HIP call); GFLOP/s = 2 R^2 G / time (the full square: the kernel computes one triangle):")
+    for n_a, n_b, G in CELLCORR_SHAPES:
+        R, ld = n_a + n_b, (G + 3) // 4 * 4  # rows as the engine's xhat buffers hold them: 16-byte regular
+        a = torch.zeros(n_a, ld, device="cuda")[:, :G]
+        b = torch.zeros(n_b, ld, device="cuda")[:, :G]
+        a.copy_(synthetic.synthetic_counts(n_a, G, seed=3, device="cuda"))
+        b.copy_(torch.relu(synthetic.synthetic_counts(n_b, G, seed=4, device="cuda") + 0.25 * torch.randn(n_b, G, device="cuda")))
+        ac, bc = a.contiguous(), b.contiguous()
+        out = torch.empty(R, R, device="cuda")
+        stacked = torch.cat([ac, bc], 0)
+        stacked64 = stacked.double()
+        rows = [("mmvae_stats_row_corr_f32, padded rows (16-byte loads)", timed(lambda: ops.row_corrcoef(a, b, out=out), reps)),
+                ("mmvae_stats_row_corr_f32, block means only (no matrix)", timed(lambda: ops.row_corrcoef(a, b, want_matrix=False), reps))]
+        if G % 4:
+            rows.append(("mmvae_stats_row_corr_f32, contiguous (element-wise)", timed(lambda: ops.row_corrcoef(ac, bc, out=out), reps)))
+        slow = max(reps // 10, 5)
+        rows.append(("torch.cat of the two operands (the stacked copy)", timed(lambda: torch.cat([ac, bc], 0), reps)))
+        rows.append(("torch.corrcoef, fp32, on the stacked copy", timed(lambda: torch.corrcoef(stacked), slow)))
+        rows.append(("torch.corrcoef, fp64, on the stacked copy", timed(lambda: torch.corrcoef(stacked64), slow)))
+        corr, stats = ops.row_corrcoef(a, b)
+        want = torch.corrcoef(stacked64)
+        live = ~torch.isnan(want)
+        err = float((corr.double()[live] - want[live]).abs().max())
+        err32 = float((torch.corrcoef(stacked).double()[live] - want[live]).abs().max())
+        s = stats.cpu().numpy()
+        print(f"  ({n_a} + {n_b}, {G}): {int(s[4] + s[5])} constant rows, cis {s[0]:.6f} cross {s[1]:.6f} comb {s[2]:.6f} "
+              f"rel {s[3]:.6f}; max |corr - fp64 torch.corrcoef| {err:.2e} (fp32 torch.corrcoef: {err32:.2e})")
+        for name, us in rows:
+            print(f"    {name:<56s} {us:9.1f} us   {2.0 * R * R * G / us / 1e3:9.1f} GFLOP/s")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--leg", choices=list(LEGS), help="run ONE leg in this process (what the driver starts)")
@@ -127,6 +171,8 @@ def main():
         print(f"# {torch.cuda.get_device_name(0)}, HIP {torch.version.hip}, torch {torch.__version__}")
         if a.leg == "pearson":
             leg_pearson(a.reps)
+        elif a.leg == "cellcorr":
+            leg_cellcorr(a.reps)
         else:
             leg_step(a.leg.split("-")[1], a.blocks, a.steps)
         return
