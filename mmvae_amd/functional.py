@@ -309,3 +309,46 @@ def row_corrcoef(a: torch.Tensor, b: Optional[torch.Tensor] = None, *, want_matr
     stats[0], stats[1], stats[2], stats[3] = cis, cross, comb, 2.0 * comb / (cis + cross)
     stats[4], stats[5] = constant[:n_a].sum(), constant[n_a:].sum()
     return (corr if want_matrix else None), stats
+
+
+def meta_disc_tail(pre1: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, W3: torch.Tensor, b3: torch.Tensor,
+                   y: Optional[torch.Tensor] = None, *, train: bool = False):
+    """A meta-discriminator (runners/meta_discriminators.py:16-55, :131-163) behind its first layer, with its loss and
+    its backward: (p, out, dpre1, grads).
+
+        h1 = sigmoid(pre1)    h2 = sigmoid(h1 W2^T + b2)    s = h2 . W3 + b3    p = sigmoid(s)          p: [B]
+        loss_row = y min(softplus(-s), 100) + (1 - y) min(softplus(s), 100)   (torch's -log clamped at -100)
+        out = [mean of loss_row, fraction of rows with (p > 0.5) == (y > 0.5)]             (None without y)
+
+    train=True: the gradients of that MEAN, ds = (p - y) / B chained back: dpre1 [B, H1] and grads = (db1, dW2, db2,
+    dW3, db3) in the shapes of the parameters; both None otherwise.  This is F.binary_cross_entropy(reduction="mean")
+    under autograd wherever p (1 - p) >= 1e-12; past that torch clamps the gradient away, this one stays p - y (formed
+    as (1 - y) sigmoid(s) - y sigmoid(-s); sigmoid' as sigmoid(x) sigmoid(-x), so that no tail cancels).
+    Device tensors: the two HIP launches of libmmvae_disc.so (ops.disc_tail, fp32).  CPU tensors only under
+    backend.cpu_plumbing(): this statement in fp64, returned as fp64 -- the tested definition."""
+    from . import backend
+
+    if backend.on_hip(pre1):
+        return ops.disc_tail(pre1, W2, b2, W3, b3, y, train=train)
+    sig, sp = torch.sigmoid, torch.nn.functional.softplus
+    x, w2, w3 = pre1.double(), W2.double(), W3.double().reshape(-1)
+    B = x.shape[0]
+    h1 = sig(x)
+    a2 = h1 @ w2.T + b2.double()
+    h2 = sig(a2)
+    s = h2 @ w3 + b3.double().reshape(())
+    p = sig(s)
+    if y is None:
+        if train:
+            raise ValueError("meta_disc_tail: train=True needs y")
+        return p, None, None, None
+    yd = y.double().reshape(-1)
+    loss_row = yd * sp(-s).clamp(max=100.0) + (1.0 - yd) * sp(s).clamp(max=100.0)
+    out = torch.stack([loss_row.mean(), ((p > 0.5) == (yd > 0.5)).double().mean()])
+    if not train:
+        return p, out, None, None
+    ds = ((1.0 - yd) * p - yd * sig(-s)) / B
+    da2 = ds[:, None] * w3[None, :] * h2 * sig(-a2)
+    dpre1 = (da2 @ w2) * h1 * sig(-x)
+    grads = (dpre1.sum(0), da2.T @ h1, da2.sum(0), (h2.T @ ds).reshape(W3.shape), ds.sum().reshape(1))
+    return p, out, dpre1, grads

@@ -994,3 +994,70 @@ def row_corrcoef(a: torch.Tensor, b: Optional[torch.Tensor] = None, *, want_matr
     _lib.check(lib.mmvae_stats_row_corr_f32(n_a, n_b, G, _ptr(a), lda, _ptr(b), ldb, _ptr(corr), ldc, _ptr(stats),
                                             _ptr(ws), nbytes, _stream()), "mmvae_stats_row_corr_f32")
     return corr, stats
+
+
+def disc_tail(pre1: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, W3: torch.Tensor, b3: torch.Tensor,
+              y: Optional[torch.Tensor] = None, *, train: bool = False, want_p: bool = True,
+              dpre1: Optional[torch.Tensor] = None, grads=None, out: Optional[torch.Tensor] = None):
+    """A meta-discriminator behind its first layer (mmvae_disc_tail_f32 of libmmvae_disc.so, two launches): h1 =
+    sigmoid(pre1), h2 = sigmoid(h1 W2^T + b2), p = sigmoid(h2 . W3 + b3), the mean binary cross-entropy against `y` and,
+    with train=True, every gradient of that mean.  pre1 [B, H1] (any row stride), W2 [H2, H1], b2 [H2], W3 [H2] or
+    [1, H2], b3 [1], y [B] in [0, 1]; H1 <= 256, H2 <= 128, H1 H2 <= 16384.
+    Returns (p, out, dpre1, grads): p [B] (None with want_p=False), out = device float32[2] (mean loss, accuracy; None
+    without y), dpre1 [B, H1] and grads = (db1, dW2, db2, dW3, db3), both None unless train.  `dpre1`, `grads` (the five
+    contiguous tensors, e.g. views of a gradient arena) and `out` are written in place when given; gradients are
+    written, not accumulated.  Forward-only p and out carry the bits of the training call."""
+    from . import _disc_lib
+
+    lib = _disc_lib.load_disc()
+    for n_, t_ in (("pre1", pre1), ("W2", W2), ("b2", b2), ("W3", W3), ("b3", b3), ("y", y), ("dpre1", dpre1), ("out", out)):
+        _chk(t_, n_)
+    B, H1, ld1 = _mat(pre1, "pre1")
+    H2 = b2.numel()
+    if tuple(W2.shape) != (H2, H1) or W3.numel() != H2 or b3.numel() != 1:
+        raise ValueError(f"disc_tail: pre1 {tuple(pre1.shape)}, W2 {tuple(W2.shape)}, b2 {tuple(b2.shape)}, "
+                         f"W3 {tuple(W3.shape)}, b3 {tuple(b3.shape)}")
+    for n_, t_ in (("W2", W2), ("b2", b2), ("W3", W3), ("b3", b3)):
+        if not t_.is_contiguous() or t_.device != pre1.device:
+            raise ValueError(f"disc_tail: {n_} must be contiguous and on {pre1.device}")
+    if y is not None and (y.numel() != B or not y.is_contiguous() or y.device != pre1.device):
+        raise ValueError(f"disc_tail: y must be a contiguous [{B}] tensor on {pre1.device}")
+    if train and y is None:
+        raise ValueError("disc_tail: train=True needs y")
+    if not train and (dpre1 is not None or grads is not None):
+        raise ValueError("disc_tail: dpre1 / grads given with train=False")
+    if y is None and not want_p:
+        raise ValueError("disc_tail: nothing to compute (no y, want_p=False)")
+    dev = pre1.device
+    p = torch.empty((B,), dtype=torch.float32, device=dev) if want_p else None
+    if y is None:
+        if out is not None:
+            raise ValueError("disc_tail: out given without y")
+    elif out is None:
+        out = torch.empty((2,), dtype=torch.float32, device=dev)
+    elif out.numel() != 2 or not out.is_contiguous():
+        raise ValueError("disc_tail: out must be a contiguous float32[2]")
+    ldd = 0
+    if train:
+        if dpre1 is None:
+            dpre1 = torch.empty((B, H1), dtype=torch.float32, device=dev)
+        Bd, Hd, ldd = _mat(dpre1, "dpre1")
+        if (Bd, Hd) != (B, H1):
+            raise ValueError(f"disc_tail: dpre1 {tuple(dpre1.shape)} != {(B, H1)}")
+        shapes = ((H1,), tuple(W2.shape), (H2,), tuple(W3.shape), (1,))
+        if grads is None:
+            grads = tuple(torch.empty(s, dtype=torch.float32, device=dev) for s in shapes)
+        grads = tuple(grads)
+        if len(grads) != 5:
+            raise ValueError("disc_tail: grads = (db1, dW2, db2, dW3, db3)")
+        for g, s, n_ in zip(grads, shapes, ("db1", "dW2", "db2", "dW3", "db3")):
+            _chk(g, n_)
+            if tuple(g.shape) != s or not g.is_contiguous() or g.device != dev:
+                raise ValueError(f"disc_tail: {n_} must be a contiguous {s} tensor on {dev}")
+    gp = [_ptr(g) for g in grads] if train else [None] * 5
+    nbytes = lib.mmvae_disc_tail_workspace_bytes(B, H1, H2)
+    ws = workspace(nbytes, dev, kind="disc_tail") if nbytes else None
+    _lib.check(lib.mmvae_disc_tail_f32(B, H1, H2, _ptr(pre1), ld1, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(y), _ptr(p),
+                                       _ptr(out), _ptr(dpre1), ldd, *gp, _ptr(ws), nbytes, _stream()),
+               "mmvae_disc_tail_f32")
+    return p, out, dpre1, grads

@@ -185,3 +185,15 @@ class Trainer:
             rows.append({"group_id": group_id, "num_samples": int(batch_a[0].shape[0]), **stats, **cats})
         table = pd.DataFrame(rows)
         return table.sort_values("group_id").reset_index(drop=True) if rows else table
+
+    @torch.no_grad()
+    def meta_discriminators(self, model, batches, **kw) -> list:
+        """The meta-discriminators of runners/meta_discriminators.py trained against the frozen model
+        (`modules.meta_discriminator.train_meta_discriminators`; `kw`: num_epochs, lr, hidden, labels, include_cis,
+        discriminators): one dict per epoch with "meta_disc/md_latent" and "meta_disc/md_<source expert>".  `batches`: a
+        re-iterable of `(x, metadata, expert_id)` or a callable returning one epoch's iterable."""
+        from .modules.meta_discriminator import train_meta_discriminators
+
+        model.eval()
+        model.trainer.set_stage("prediction")
+        return train_meta_discriminators(model, batches, **kw)

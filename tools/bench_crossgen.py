@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Cross-generation and the statistics computed on it, measured.
 
-Four legs, each in a child process of its own under its own time limit (a leg that faults, aborts or runs out of time
+Five legs, each in a child process of its own under its own time limit (a leg that faults, aborts or runs out of time
 ends the run: nothing more is started on the device):
 
   step-c2    ms per CMMVAEModel.cross_generate_step to ALL experts, captured engine against the module path, interleaved
@@ -13,6 +13,10 @@ ends the run: nothing more is started on the device):
   cellcorr   us of mmvae_stats_row_corr_f32 (cell-by-cell correlation of a cis on a cross generation and its block
              means) at (100 + 100, 20 000), (100 + 100, 60 530), (512 + 512, 20 000), and of torch.corrcoef on the device
              in fp32 and in fp64 on the stacked copy, the copy's time listed separately
+  metadisc   ms per MetaDiscriminators.step (cross-generation, the latent discriminator and the other expert's
+             discriminator: GEMM, fused tail kernel, GEMM, fused Adam each) at C2 and at the reference's gene counts,
+             B = 512, against the same step done with nn.Sequential + torch.optim.Adam on the device, interleaved blocks;
+             and us of one train_step of the gene-wide discriminator alone against its stock-torch counterpart
 
 Nothing is asserted: the numbers are reported.  Output: the lines below, also written to --out (default
 profiles/crossgen.txt)."""
@@ -28,7 +32,7 @@ sys.path.insert(0, ROOT)
 GENES = {"c2": {"human": 20000, "mouse": 20000}, "full": {"human": 60530, "mouse": 52437}}
 PEARSON_SHAPES = [(100, 60530), (512, 20000), (512, 60530)]
 CELLCORR_SHAPES = [(100, 100, 20000), (100, 100, 60530), (512, 512, 20000)]
-LEGS = {"step-c2": 240, "step-full": 300, "pearson": 240, "cellcorr": 240}  # seconds
+LEGS = {"step-c2": 240, "step-full": 300, "pearson": 240, "cellcorr": 240, "metadisc": 420}  # seconds
 
 
 def leg_step(which: str, blocks: int, steps: int):
@@ -154,6 +158,77 @@ def leg_cellcorr(reps: int):
             print(f"    {name:<56s} {us:9.1f} us   {2.0 * R * R * G / us / 1e3:9.1f} GFLOP/s")
 
 
+def leg_metadisc(blocks: int, steps: int, reps: int):
+    import pandas as pd
+    import torch
+    import torch.nn.functional as F
+
+    from mmvae_amd import synthetic
+    from mmvae_amd.modules.meta_discriminator import MetaDiscriminators
+
+    B = 512
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    for which, genes in GENES.items():
+        model = synthetic.build_model(genes, use_engine=True, seed=0).cuda()
+        model.eval()
+        model.trainer.set_stage("prediction")
+        eids = list(genes)
+        xs = {e: synthetic.synthetic_counts(B, G, seed=7 + i, device="cuda") for i, (e, G) in enumerate(genes.items())}
+        frames = {e: pd.DataFrame({"cell": range(B)}) for e in eids}
+        torch.manual_seed(0)
+        mds = MetaDiscriminators(model)
+        stock = {k: d.as_sequential().cuda() for k, d in mds.discriminators.items()}
+        sopt = {k: torch.optim.Adam(v.parameters(), lr=1e-3) for k, v in stock.items()}
+        truth = {e: torch.full((B, 1), mds.labels[e], device="cuda") for e in eids}
+
+        def stock_train(name, matrix, y):
+            sopt[name].zero_grad(set_to_none=True)
+            with torch.enable_grad():
+                loss = F.binary_cross_entropy(stock[name](matrix), y, reduction="mean")
+                loss.backward()
+            sopt[name].step()
+            return loss
+
+        def stock_step(e):
+            others = [t for t in eids if t != e]
+            out = model.cross_generate_step((xs[e], frames[e], e), targets=others)
+            stock_train("latent", out["z"][0], truth[e])
+            for t in others:
+                stock_train(t, out[f"xhat_{t}"][0], truth[e])
+
+        def block(ours: bool, n: int) -> float:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(n):
+                e = eids[i % len(eids)]
+                if ours:
+                    mds.step((xs[e], frames[e], e))
+                else:
+                    stock_step(e)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / n * 1e3
+
+        for ours in (True, False):
+            block(ours, 8 * len(eids))
+        a, b = [], []
+        for _ in range(blocks):
+            a.append(block(True, steps))
+            b.append(block(False, steps))
+        print(f"MetaDiscriminators.step, {which} ({'/'.join(str(g) for g in genes.values())} genes, B = {B}, hidden 128/64), "
+              f"{blocks} interleaved blocks of {steps} steps:")
+        print(f"  HIP (GEMM + fused tail + GEMM + fused Adam) : {med(a):8.3f} ms / step   (blocks {' '.join(f'{v:.3f}' for v in a)})")
+        print(f"  nn.Sequential + torch.optim.Adam            : {med(b):8.3f} ms / step   (blocks {' '.join(f'{v:.3f}' for v in b)})")
+        print(f"  stock / HIP                                 : {med(b) / med(a):8.2f} x")
+        t = eids[1]
+        xhat = model.cross_generate_step((xs[eids[0]], frames[eids[0]], eids[0]), targets=[t])[f"xhat_{t}"][0]
+        us_hip = timed(lambda: mds[t].train_step(xhat, 0.0), reps)
+        us_stock = timed(lambda: stock_train(t, xhat, truth[eids[0]]), reps)
+        us_lat = timed(lambda: mds["latent"].train_step(xs[eids[0]][:, :mds["latent"].in_features].contiguous(), 0.0), reps)
+        print(f"  one train_step of the {genes[t]}-wide discriminator alone, {reps} back-to-back calls: HIP {us_hip:9.1f} us, "
+              f"stock torch {us_stock:9.1f} us ({us_stock / us_hip:.2f} x); the latent discriminator: HIP {us_lat:9.1f} us")
+        del model, mds, stock, sopt
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--leg", choices=list(LEGS), help="run ONE leg in this process (what the driver starts)")
@@ -173,6 +248,8 @@ def main():
             leg_pearson(a.reps)
         elif a.leg == "cellcorr":
             leg_cellcorr(a.reps)
+        elif a.leg == "metadisc":
+            leg_metadisc(a.blocks, a.steps, a.reps)
         else:
             leg_step(a.leg.split("-")[1], a.blocks, a.steps)
         return
