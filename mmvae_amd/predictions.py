@@ -50,6 +50,7 @@ _SIGNATURES = {
     "H5Gclose": (herr_t, [hid_t]),
     "H5Gget_info": (herr_t, [hid_t, ctypes.c_void_p]),
     "H5Lexists": (htri_t, [hid_t, ctypes.c_char_p, hid_t]),
+    "H5Ldelete": (herr_t, [hid_t, ctypes.c_char_p, hid_t]),
     "H5Lget_name_by_idx": (ctypes.c_ssize_t, [hid_t, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, hsize_t,
                                               ctypes.c_char_p, ctypes.c_size_t, hid_t]),
     "H5Screate_simple": (hid_t, [ctypes.c_int, _P(hsize_t), _P(hsize_t)]),
@@ -355,6 +356,37 @@ def load_from_hdf5(hdf5_filepath: str, key: str):
         if _exists(g, RK.UMAP_EMBEDDINGS):
             embedding = _read_dataset(g, RK.UMAP_EMBEDDINGS)
     return data, metadata, embedding
+
+
+def write_umap_embeddings(hdf5_filepath: str, key: str, embedding) -> None:
+    """Store `embedding` [N, C] (tensor or array) as `/<key>/umap_embeddings`, replacing a dataset already there, as
+    plot_umap_h5 does (runners/umap_predictions.py:133-148: fixed shape, the array's own float type).  The group must
+    exist -- it is the one the predictions were written under; `load_from_hdf5` reads the dataset back."""
+    if hasattr(embedding, "detach"):
+        embedding = embedding.detach().cpu().numpy()
+    emb = np.ascontiguousarray(embedding)
+    if emb.ndim != 2 or emb.dtype.kind != "f":
+        raise ValueError(f"write_umap_embeddings: expected a 2-D float array, got {emb.dtype} {emb.shape}")
+    kind = "f32" if emb.dtype == np.float32 else "float"
+    if kind == "float":
+        emb = emb.astype(np.float64)
+    if not os.path.exists(hdf5_filepath):
+        raise FileNotFoundError(hdf5_filepath)
+    h5 = hdf5_lib()
+    name = RK.UMAP_EMBEDDINGS
+    with _open_file(hdf5_filepath, "a") as f:
+        if not _exists(f, key):
+            raise KeyError(f"{key} not found in {hdf5_filepath}")
+        with _group(f, key, create=False) as g:
+            if _exists(g, name):
+                _check(h5.H5Ldelete(g, name.encode(), H5P_DEFAULT), f"delete {key}/{name}")
+            dims = _dims(*emb.shape)
+            with _mem_type(kind) as t, \
+                    _Handle(h5.H5Screate_simple(emb.ndim, dims, dims), "H5Sclose", "dataspace") as sp, \
+                    _Handle(h5.H5Dcreate2(g, name.encode(), t, sp, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT), "H5Dclose",
+                            f"create dataset {name}") as ds:
+                if emb.size:
+                    _check(h5.H5Dwrite(ds, t, H5S_ALL, H5S_ALL, H5P_DEFAULT, _buffer(kind, emb)), f"write {name}")
 
 
 class PredictionWriter:

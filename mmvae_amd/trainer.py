@@ -165,6 +165,25 @@ class Trainer:
         return []
 
     @torch.no_grad()
+    def umap(self, model, batches: Iterable, **kw):
+        """(embedding [cells, n_components], metadata) of the UMAP of the latent embeddings: `predict_step` over the
+        batches with z kept where it was produced, then `mmvae_amd.umap.umap_embeddings(z, **kw)` (the reference's
+        runners/umap_predictions.py:25-50, there on the host from predictions.h5).  metadata is the batches' frames
+        stacked, one row per cell, with the "species" column predict_step adds;
+        `predictions.write_umap_embeddings` stores the embedding next to the predictions."""
+        import pandas as pd
+
+        from .constants import REGISTRY_KEYS as RK
+        from .umap import umap_embeddings
+
+        outs = [p[RK.Z] for p in self.predict(model, batches)]
+        if not outs:
+            raise ValueError("Trainer.umap: no batches")
+        z = torch.cat([o[0] for o in outs], 0)
+        metadata = pd.concat([o[1] for o in outs], ignore_index=True)
+        return umap_embeddings(z, **kw), metadata
+
+    @torch.no_grad()
     def correlations(self, model, groups: Iterable, decimals: Optional[int] = 3):
         """The table of get_correlations (runners/run_correlations.py:95-145) as a pandas.DataFrame, one row per group of
         `groups` = (group_id, batch_a, batch_b) with the two batches of different experts
