@@ -67,6 +67,10 @@ class BaseModel(_Base):
         self.record_gradients = record_gradients
         self.save_gradients_interval = save_gradients_interval
         self.gradient_record_cap = gradient_record_cap
+        # save_gradients(): {"gradients/<named parameter>": add_histogram_raw arguments} of the latest recorded step
+        self.gradient_histograms: dict = {}
+        self.gradient_histograms_step: Optional[int] = None
+        self._gradient_warnings: set = set()
         self.predict_dir = predict_dir
         self.predict_save_interval = predict_save_interval
         self._curr_save_idx = initial_save_index
@@ -196,6 +200,75 @@ class BaseModel(_Base):
                         if p.grad is not None:
                             sq += float(p.grad.data.norm(2)) ** 2
                 self.log(f"{tag_prefix}/{name}", sq ** 0.5)
+
+    # ------------------------------------------------------------------ gradient histograms (base_model.py:178-231)
+    def gradients_due(self) -> bool:
+        """The check of the reference's on_before_optimizer_step (:205-231): recording is switched on, a trainer is
+        present and not evaluating, and its global_step is a multiple of save_gradients_interval."""
+        t = self.trainer if (HAVE_LIGHTNING is False or getattr(self, "_trainer", None) is not None) else None
+        if not self.record_gradients or t is None:
+            return False
+        evaluating = getattr(t, "evaluating", None)
+        if evaluating is None:
+            evaluating = any(getattr(t, f, False) for f in ("validating", "testing", "predicting", "sanity_checking"))
+        return not evaluating and int(t.global_step) % max(int(self.save_gradients_interval), 1) == 0
+
+    def _warn_gradients_once(self, why: str) -> None:
+        if why not in self._gradient_warnings:
+            import warnings
+
+            self._gradient_warnings.add(why)
+            warnings.warn(f"mmvae_amd: record_gradients is set but gradients are not recorded: {why}")
+
+    def save_gradients(self, optimizers=None, skip_inactive: bool = False) -> None:
+        """One histogram per named parameter of `optimizers` (default: every optimiser of the model), as the reference's
+        save_gradients() sends them to the logger (:192-203), tagged `gradients/<name>` with <name> from
+        named_parameters().  Each optimiser's gradient arena is read once on the device
+        (HipAdam.grad_histograms: libmmvae_hist.so over TensorBoard's default edges) and ONE copy per optimiser brings
+        the counts and moments to the host.  The result replaces `self.gradient_histograms` ({tag: the keyword
+        arguments of SummaryWriter.add_histogram_raw}; `gradient_histograms_step` is the trainer's global_step); when
+        `self.logger.experiment` has add_histogram_raw it is called per tag with that step (add_histogram with the
+        gradient itself when that is all it has).  Nothing of TensorBoard is imported.
+
+        The reference's rule for large models is kept: more named parameters than `gradient_record_cap` switches
+        recording off for good (record_gradients = False) and writes nothing.
+        Differences: the moments describe the finite values (mmvae_amd.histogram); a parameter whose gradient holds no
+        finite value inside the edges gets no histogram; `skip_inactive` leaves out the parameters without a gradient in
+        this step (the reference's `v.grad is not None`).  Under data parallelism (world size > 1) nothing is recorded,
+        with one warning: the gradient exchange rewrites the arena in place, sharded for the experts."""
+        named = list(self.named_parameters())
+        if len(named) > self.gradient_record_cap:
+            self.record_gradients = False
+            return
+        from .. import dist as mdist
+
+        if mdist.world_size() > 1:
+            return self._warn_gradients_once("histograms under data parallelism are not implemented")
+        name_of = {id(p): n for n, p in named}
+        step = int(getattr(self.trainer, "global_step", 0) or 0)
+        passes = []
+        for opt in (self.optimizers() if optimizers is None else optimizers):
+            if not hasattr(opt, "grad_histograms"):
+                self._warn_gradients_once(f"{type(opt).__name__} keeps no gradient arena")
+                continue
+            names = [name_of.get(id(p)) for p in opt.arena.params]
+            skip = set(getattr(opt, "_inactive", ())) if skip_inactive else set()
+            passes.append((opt, opt.grad_histograms(names=names), skip))  # enqueued: the copies come behind all passes
+        experiment = getattr(getattr(self, "logger", None), "experiment", None)
+        found = {}
+        for opt, hist, skip in passes:
+            host = hist.cpu()
+            for i, name in enumerate(hist.names):
+                raw = host.tensorboard_raw(i) if (name is not None and i not in skip) else None
+                if raw is None:
+                    continue
+                tag = f"gradients/{name}"
+                found[tag] = raw
+                if hasattr(experiment, "add_histogram_raw"):
+                    experiment.add_histogram_raw(tag, global_step=step, **raw)
+                elif hasattr(experiment, "add_histogram"):
+                    experiment.add_histogram(tag=tag, values=opt.arena.grad_view(i) * opt.grad_scale, global_step=step)
+        self.gradient_histograms, self.gradient_histograms_step = found, step
 
     def auto_log(self, log_dict: dict, tags: Iterable[str] = (), sep: str = "/",
                  key_pos: Literal["first", "last"] = "first", log_sanity_checking: bool = False):

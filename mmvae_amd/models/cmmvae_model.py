@@ -129,6 +129,8 @@ class CMMVAEModel(BaseModel):
         self._apply_lr_schedule()
         if engine is not None:
             engine.training_step(x, metadata, expert_id, next_batch=hint)
+            if self.gradients_due():
+                self._save_engine_gradients(engine, expert_id)
             return self._advance_lr_schedule()
         self._flush_engine()  # (a step on the module path behind engine steps: their deferred updates land first)
         if getattr(self.module.vae.encoder, "elbo_mode", "analytic") != "analytic":
@@ -158,6 +160,8 @@ class CMMVAEModel(BaseModel):
             self.log_gradient_norms({name: optimizer}, tag_prefix="grad_norms")
         for key, optimizer in adversary_optims.items():  # gradients the main backward left on the adversaries: logged,
             self.log_gradient_norms({f"generator_{key}": optimizer}, tag_prefix="grad_norms")  # never stepped
+        if self.gradients_due():  # behind the norms (a HipAdam gathers its arena there), in front of the steps
+            self.save_gradients([o for o, _ in stepped.values()], skip_inactive=True)
         for optimizer, rule in stepped.values():
             if rule:
                 self.clip_gradients(optimizer, *rule)
@@ -166,6 +170,24 @@ class CMMVAEModel(BaseModel):
         self.kl_annealing_fn.step()
         self.auto_log(terms, tags=[self.stage_name, expert_id])
         self._advance_lr_schedule()
+
+    def _save_engine_gradients(self, engine, expert_id: str) -> None:
+        """save_gradients() behind a step of the captured engine: the histogram passes are launched on the current stream
+        behind the replay, outside every captured program.  Recorded are the optimisers the step updates and whose
+        arenas hold the step's whole pre-clip gradient when the replay has been enqueued: the VAE's and the active
+        expert's (DESIGN.md section 6d gives the argument: every gradient kernel of the program precedes the
+        optimisers' norm pass in stream order, and the norm, clip and Adam kernels take the gradient as `const float*`
+        -- the clip coefficient is applied inside the update, never written back).  The adversaries' parameters are left
+        out: the fused adversary passes keep no generator-pass gradient of them.  Not recorded, with one warning:
+        models with conditional layers (the condition blocks absent from a batch keep an earlier step's gradient in the
+        arena) and data parallelism (BaseModel.save_gradients)."""
+        if getattr(self.module.vae, "conditionals", None) is not None:
+            return self._warn_gradients_once("the captured engine leaves earlier steps' gradients in the arena slices of "
+                                             "condition blocks absent from the batch (use_engine=False records them)")
+        if engine.overlap:  # (a deferred expert update on the communication stream: joined first; it only reads the arena)
+            engine.flush()
+        live = self.get_optimizers()
+        self.save_gradients([live["vae"], live["experts"][expert_id]])
 
     def _apply_lr_schedule(self) -> None:
         """With a schedule: every optimiser's lr = its base lr x factor(t) ahead of training step t (t = the schedule's

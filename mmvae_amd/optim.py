@@ -96,6 +96,11 @@ class ParamArena:
     def grad_view(self, i: int) -> torch.Tensor:
         return self.view(self.grad, i)
 
+    def segments(self):
+        """(offsets, numels) of the parameters inside the arenas, in parameter order (elements; a group's members lie
+        back to back, so an offset need not be a multiple of 4)."""
+        return list(self.offsets), [p.numel() for p in self.params]
+
     def gather_grads(self, direct=(), zeroed: bool = False, only=None) -> List[int]:
         """Bring autograd-produced .grad tensors into the gradient arena (D2D copies; no-ops for arena views).
         Returns the indices of the parameters WITHOUT a gradient (their arena slice is zeroed, so the global norm is
@@ -291,6 +296,26 @@ class HipAdam(torch.optim.Optimizer):
             for i in self.managed - self._direct:
                 self.arena.grad_view(i).zero_()
         return inactive + sorted(self.managed - self._direct)
+
+    def grad_histograms(self, names=None, edges=None):
+        """Histogram and moments of every parameter's gradient as the gradient arena holds it NOW, from one pass over the
+        arena (mmvae_amd.histogram.segment_histograms over ParamArena.segments(); edges default to TensorBoard's).
+        The values are the arena's times `grad_scale` -- the factor the norm and the Adam kernels apply when they read
+        it (1 / world size under data parallelism, else 1) -- so sqrt(sum of sum_squares) is the pre-clip norm that
+        compute_grad_norm() reports.  `names`: one name per parameter, kept as `.names` of the result (default: the arena
+        indices).  The result stays on the device until `.cpu()`; nothing is synchronised here.  The arena is only read."""
+        from .histogram import segment_histograms
+
+        offsets, numels = self.arena.segments()
+        names = list(range(len(offsets))) if names is None else list(names)
+        if len(names) != len(offsets):
+            raise ValueError(f"grad_histograms: {len(names)} names for {len(offsets)} parameters")
+        if not hasattr(self, "_hist_cache"):
+            self._hist_cache: dict = {}
+        out = segment_histograms(self.arena.grad, offsets, numels, edges=edges, scale=float(self.grad_scale),
+                                 cache=self._hist_cache)
+        out.names = names
+        return out
 
     def note_direct_grads(self, indices) -> None:
         """The gradients of these parameters (arena indices) were written straight into the gradient arena by a kernel
