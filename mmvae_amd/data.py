@@ -313,13 +313,21 @@ class SpeciesChunks:
     `device_chunks=True` (needs a GPU `device`): chunks are uploaded once and batches gathered on the device by one HIP
     launch each (`_iter_device`); same batches.  `device_chunk_bytes`: budget of one resident chunk (default: a quarter
     of the free device memory when the iterator starts); at most two chunks are resident, a chunk over the budget is
-    gathered on the host (one warning per object)."""
+    gathered on the host (one warning per object).
+
+    `normalize="log1p_cpm"` (default None: the files hold what the model trains on already): the chunk files hold RAW
+    counts and every batch is normalised on its way out, v <- log1p(target_sum * v / rowsum) per cell
+    (mmvae_amd.preprocess: the reference's normalize_data).  A device-resident chunk is normalised once, where it lies, by
+    one launch behind its upload; a host-gathered batch by the same kernel over its CSR values on the producing stream
+    (numpy on a CPU `device`).  A row's result depends on that row's values in their stored order alone, so both paths
+    yield the same batches bit for bit.  Files that do not look like raw counts draw one RuntimeWarning per object."""
 
     def __init__(self, directory_path: str, npz_masks, metadata_masks, batch_size: int, name: str,
                  allow_partials: bool = False, shuffle: bool = True, return_dense: bool = False, seed: int = 0,
                  device: Optional[Union[str, torch.device]] = None, prefetch: bool = True, rank: int = 0, world: int = 1,
                  workers: int = 3, gather_threads: int = 2, index_dtype: torch.dtype = torch.int32,
-                 device_chunks: bool = False, device_chunk_bytes: Optional[int] = None):
+                 device_chunks: bool = False, device_chunk_bytes: Optional[int] = None, normalize: Optional[str] = None,
+                 target_sum: float = 1e4):
         self.chunks = list_chunks(directory_path, npz_masks, metadata_masks)
         self.batch_size = int(batch_size)
         self.name = name
@@ -347,6 +355,25 @@ class SpeciesChunks:
             raise ValueError("device_chunk_bytes must not be negative")
         self.device_chunk_bytes = None if device_chunk_bytes is None else int(device_chunk_bytes)
         self._warned_budget = False
+        # raw-count chunks (opt-in): see _tensor / _upload_chunk
+        from . import preprocess
+
+        if normalize is not None and normalize not in preprocess.NORMALIZE_MODES:
+            raise ValueError(f"normalize must be None or one of {preprocess.NORMALIZE_MODES}, got {normalize!r}")
+        self.normalize = normalize
+        self.target_sum = preprocess.check_target_sum(target_sum)
+        self._checked_raw = False
+
+    def _check_raw(self, matrix, where: str) -> None:
+        """Guard against normalising twice: once per object, the first stored values of the first chunk loaded are looked
+        at on the host; anything but non-negative integers draws one RuntimeWarning."""
+        if self.normalize is None or self._checked_raw:
+            return
+        self._checked_raw = True
+        head = np.asarray(matrix.data[:min(len(matrix.data), 65536)])
+        if head.size and bool(((head < 0) | (head != np.floor(head))).any()):
+            warnings.warn(f"{where}: normalize={self.normalize!r} but the chunk does not look like raw counts (stored "
+                          "values that are not non-negative integers): is it normalised already?", RuntimeWarning)
 
     # ---- chunks: (scipy CSR over the mapped file, metadata, row order)
     def _prepared_chunks(self, rng: np.random.Generator) -> Iterator:
@@ -355,6 +382,7 @@ class SpeciesChunks:
             order = [int(i) for i in rng.permutation(len(order))]
         for ci in order:
             matrix, metadata = load_chunk(*self.chunks[ci])
+            self._check_raw(matrix, self.chunks[ci][0])
             rows = rng.permutation(matrix.shape[0]) if self.shuffle else np.arange(matrix.shape[0])
             yield matrix, metadata, rows.astype(np.int64)
 
@@ -439,6 +467,15 @@ class SpeciesChunks:
             slot.event.record()
         else:  # host batches own their arrays: the slot was allocated for this batch alone (see __iter__)
             slot.crow, slot.col, slot.val = slot.crow.new_empty(0), slot.col.new_empty(0), slot.val.new_empty(0)
+        if self.normalize is not None and n_rows:  # raw counts: normalised here, before the batch is densified
+            if val.is_cuda:
+                from . import ops
+
+                ops.csr_log1p_normalize_(crow, val, self.target_sum)
+            else:
+                from . import preprocess
+
+                preprocess._normalize_cpu(crow.numpy(), val.numpy(), self.target_sum)
         t = torch.sparse_csr_tensor(crow, col, val, size=(n_rows, n_cols))
         if self.return_dense:
             from . import backend
@@ -555,6 +592,10 @@ class SpeciesChunks:
                 dev.append(buf[o:o + len(src) * np.dtype(np_dtype).itemsize].view(t_dtype))
             csr = torch.sparse_csr_tensor(dev[0], dev[1], dev[2], size=(n, G))
             tab = tbuf[:table.size * isz].view(self.index_dtype).view(table.shape[0], self.batch_size + 1)
+            if self.normalize is not None and n:  # raw counts: one launch behind the copies, ahead of the gathers' event
+                from . import ops
+
+                ops.csr_log1p_normalize_(dev[0], dev[2], self.target_sum, stream=stream)
             event = torch.cuda.Event()
             event.record(stream)
         staging["event"] = event
@@ -573,6 +614,7 @@ class SpeciesChunks:
         for ci in order:
             where = self.chunks[ci][0]
             matrix, metadata = load_chunk(*self.chunks[ci])
+            self._check_raw(matrix, where)
             n = matrix.shape[0]
             rows = (rng.permutation(n) if self.shuffle else np.arange(n)).astype(np.int64)
             n_batches = -(-n // self.batch_size) if self.allow_partials else n // self.batch_size

@@ -1061,3 +1061,37 @@ def disc_tail(pre1: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, W3: torch.
                                        _ptr(out), _ptr(dpre1), ldd, *gp, _ptr(ws), nbytes, _stream()),
                "mmvae_disc_tail_f32")
     return p, out, dpre1, grads
+
+
+def csr_log1p_normalize_(crow: torch.Tensor, values: torch.Tensor, target_sum: float = 1e4,
+                         row_sums: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+    """`values` (device fp32, the stored elements of a CSR matrix with the row pointers `crow`, int32 or int64) IN PLACE:
+    v <- log1p(target_sum * v / rowsum), the reference's normalize_data (mmvae_prep_csr_log1p_norm_* of
+    libmmvae_prep.so, one launch; arithmetic and the zero-sum rule: include/mmvae_prep.h).  `row_sums` [n_rows] fp32
+    receives the raw row totals when given.  Enqueued on `stream` (a torch stream or a raw handle; default: the current
+    stream); nothing is synchronised.  Returns `values`."""
+    from . import _prep_lib
+
+    lib = _prep_lib.load_prep()
+    if not crow.is_cuda or not values.is_cuda:
+        raise _lib.HipLibraryError("csr_log1p_normalize_: CPU tensors have no HIP path (mmvae_amd.preprocess.normalize_csr_ "
+                                   "takes them)")
+    _chk(values, "values")
+    _chk(row_sums, "row_sums")
+    if crow.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"csr_log1p_normalize_: row pointers must be int32 or int64, got {crow.dtype}")
+    if crow.dim() != 1 or crow.numel() < 2 or not crow.is_contiguous() or values.dim() != 1 or not values.is_contiguous():
+        raise ValueError("csr_log1p_normalize_: crow [n_rows + 1] and values [nnz] must be contiguous vectors")
+    if crow.device != values.device or (row_sums is not None and row_sums.device != values.device):
+        raise ValueError("csr_log1p_normalize_: crow, values and row_sums must be on one device")
+    n_rows, nnz = crow.numel() - 1, values.numel()
+    if row_sums is not None and (row_sums.dim() != 1 or row_sums.numel() != n_rows or not row_sums.is_contiguous()):
+        raise ValueError(f"csr_log1p_normalize_: row_sums must be a contiguous fp32 vector of {n_rows}")
+    if stream is None:
+        stream = torch.cuda.current_stream(values.device).cuda_stream
+    elif not isinstance(stream, int):
+        stream = stream.cuda_stream
+    fn = lib.mmvae_prep_csr_log1p_norm_i32 if crow.dtype == torch.int32 else lib.mmvae_prep_csr_log1p_norm_i64
+    _lib.check(fn(n_rows, nnz, crow.data_ptr(), values.data_ptr() if nnz else None, float(target_sum), _ptr(row_sums),
+                  stream), "mmvae_prep_csr_log1p_norm")
+    return values

@@ -35,6 +35,14 @@ def synthetic_counts(B: int, G: int, seed: int = 1234, device="cpu") -> torch.Te
     return x.to(device)
 
 
+def synthetic_raw_counts(B: int, G: int, seed: int = 1234, device="cpu") -> torch.Tensor:
+    """The counts `c` behind synthetic_counts(B, G, seed) (same draws), before their normalisation: what a raw census
+    chunk holds and `SpeciesChunks(normalize="log1p_cpm")` / mmvae_amd.preprocess take."""
+    g = torch.Generator().manual_seed(seed)
+    lam = 0.15 * torch.exp(torch.randn(G, generator=g))
+    return torch.poisson(lam.expand(B, G), generator=g).to(device)
+
+
 def synthetic_metadata(B: int, seed: int = 1234, classes: Optional[Dict[str, int]] = None) -> pd.DataFrame:
     classes = classes or ADV_CLASSES
     g = torch.Generator().manual_seed(seed)

@@ -4,7 +4,11 @@ loop of `bench.py --input npz`) or resident on the device (`--device-chunks 1`: 
 `mmvae_csr_gather_rows_*` launch per batch).  Same data, same model, same loop either way: eight synthetic batches per
 expert written as uncompressed npz-CSR / pkl chunks of four batches, read through SpeciesChunks ->
 MultiModalBatches(round_robin) -> Prefetcher(depth 3) -> Lookahead -> training_step.  Prints ONE JSON line (ms/step,
-cells/s).  For an A/B, alternate the two settings, one process per run, and compare medians."""
+cells/s).  For an A/B, alternate the two settings, one process per run, and compare medians.
+
+`--normalize 1`: the chunk files hold the RAW counts behind the same batches and the feed normalises them on the way
+(`SpeciesChunks(normalize="log1p_cpm")`: one launch per uploaded chunk with `--device-chunks 1`, one per batch without);
+`--normalize 0` (default) reads pre-normalised files, as before."""
 import argparse
 import json
 import os
@@ -20,6 +24,7 @@ sys.path.insert(0, ROOT)
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--device-chunks", type=int, choices=[0, 1], default=0)
+    ap.add_argument("--normalize", type=int, choices=[0, 1], default=0)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--config", default="c2", choices=["c2"])
@@ -47,13 +52,15 @@ def main():
     tmp = tempfile.mkdtemp(prefix="mmvae_bench_feed_")
     feeds = {}
     for i, (eid, G) in enumerate(cfg["experts"].items()):
-        rows = torch.cat([synthetic.synthetic_counts(B, G, seed=77 + 31 * i + j, device="cpu") for j in range(8)])
+        draw = synthetic.synthetic_raw_counts if a.normalize else synthetic.synthetic_counts
+        rows = torch.cat([draw(B, G, seed=77 + 31 * i + j, device="cpu") for j in range(8)])
         meta = pd.concat([synthetic.synthetic_metadata(B, seed=9 + j) for j in range(8)], ignore_index=True)
         mdata.write_chunks(os.path.join(tmp, eid), eid, sp.csr_matrix(rows.numpy()), meta, chunk_rows=4 * B,
                            compressed=False)
         feeds[eid] = mdata.SpeciesChunks(os.path.join(tmp, eid), f"{eid}_train_counts_*.npz",
                                          f"{eid}_train_metadata_*.pkl", B, eid, seed=i, device=device,
-                                         device_chunks=bool(a.device_chunks))
+                                         device_chunks=bool(a.device_chunks),
+                                         **(dict(normalize="log1p_cpm") if a.normalize else {}))
 
     def endless():
         while True:
@@ -96,7 +103,7 @@ def main():
     loss = {k: float(v.detach()) for k, v in model.logged.items() if k.startswith("loss/")}
     out = {"metric": "cells/sec per MMVAE train step, npz-CSR chunks streamed from disk", "unit": "cells/s",
            "value": B * a.steps / el, "ms_per_step": el / a.steps * 1e3, "ms_per_step_median": per_step[len(per_step) // 2],
-           "host_ms_per_step": host_el / a.steps * 1e3, "device_chunks": int(a.device_chunks), "steps": a.steps,
+           "host_ms_per_step": host_el / a.steps * 1e3, "device_chunks": int(a.device_chunks), "normalize": int(a.normalize), "steps": a.steps,
            "warmup": a.warmup, "config": a.config, "batch": B, "path": "engine(hipGraph)" if model._engine else "module",
            "last_losses": loss, "device": torch.cuda.get_device_name(0)}
     os.write(json_fd, (json.dumps(out) + "\n").encode())
