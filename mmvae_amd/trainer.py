@@ -184,6 +184,19 @@ class Trainer:
         return umap_embeddings(z, **kw), metadata
 
     @torch.no_grad()
+    def umap_plots(self, model, batches: Iterable, categories, save_dir: str, key: str = "z", n_largest: int = 15,
+                   method: str = "", plot_kw: Optional[dict] = None, **umap_kw) -> List[str]:
+        """`Trainer.umap`, then one `mmvae_amd.plots.plot_category` per category of `categories` (columns of the batches'
+        metadata): the files `save_dir`/integrated.{category}.umap.{key}.png, whose paths are returned.  The embedding
+        stays on the device until its raster has been made there; what reaches the host is the picture.  `plot_kw` goes to
+        plot_category (alpha, marker_size, decorate, colors, ...), every further keyword to `umap_embeddings`."""
+        from .plots import plot_category
+
+        embedding, metadata = self.umap(model, batches, **umap_kw)
+        return [plot_category(embedding, metadata, category, save_dir, n_largest, key, method, **(plot_kw or {}))
+                for category in categories]
+
+    @torch.no_grad()
     def correlations(self, model, groups: Iterable, decimals: Optional[int] = 3):
         """The table of get_correlations (runners/run_correlations.py:95-145) as a pandas.DataFrame, one row per group of
         `groups` = (group_id, batch_a, batch_b) with the two batches of different experts
