@@ -6,13 +6,10 @@ product: missing or unloadable, every call raises -- no torch fallback.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Optional
 
+from ._bind import Binding
 from ._lib import ERR_ARG, ERR_LAUNCH, OK, HipLibraryError, check  # noqa: F401  (the return codes are shared)
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-DISC_LIB_PATH = os.path.join(_HERE, "csrc", "libmmvae_disc.so")
 
 DISC_ABI_VERSION = 1
 DISC_MAX_H1 = 256
@@ -35,34 +32,17 @@ DISC_PROTOTYPES = {
     "mmvae_disc_tail_f32": (_i, [_i, _i, _i, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _z, _p]),
 }
 
+BINDING = Binding("libmmvae_disc.so", "mmvae_disc.h", DISC_PROTOTYPES, "mmvae_disc_abi_version", DISC_ABI_VERSION,
+                  "mmvae_disc_build_arch")
+DISC_LIB_PATH = BINDING.path
+
 _disc: Optional[C.CDLL] = None
 
 
 def load_disc() -> C.CDLL:
-    """Load libmmvae_disc.so (built by __graft_entry__.build() / `make -C mmvae_amd/csrc`).  Raises loudly."""
+    """Load libmmvae_disc.so (see _bind.Binding.load).  Raises loudly."""
     global _disc
     if _disc is not None:
         return _disc
-    import torch  # noqa: F401  (torch's HIP runtime must be the process's: see _lib.load)
-
-    if not os.path.exists(DISC_LIB_PATH):
-        raise HipLibraryError(
-            f"{DISC_LIB_PATH} not found: build it with `make -C mmvae_amd/csrc` (or __graft_entry__.build()). "
-            "mmvae_amd has no non-HIP execution path for device tensors."
-        )
-    try:
-        lib = C.CDLL(DISC_LIB_PATH)
-    except OSError as e:  # pragma: no cover
-        raise HipLibraryError(f"could not load {DISC_LIB_PATH}: {e}") from e
-    for name, (res, args) in DISC_PROTOTYPES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise HipLibraryError(f"{DISC_LIB_PATH} does not export {name}") from e
-        fn.restype = res
-        fn.argtypes = args
-    if lib.mmvae_disc_abi_version() != DISC_ABI_VERSION:
-        raise HipLibraryError(f"{DISC_LIB_PATH} has ABI {lib.mmvae_disc_abi_version()}, this binding was written "
-                              f"against {DISC_ABI_VERSION}: rebuild it")
-    _disc = lib
-    return lib
+    _disc = BINDING.load()
+    return _disc

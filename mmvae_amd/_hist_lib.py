@@ -8,13 +8,10 @@ unloadable, every call raises -- no torch fallback.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Optional
 
+from ._bind import Binding
 from ._lib import ERR_ARG, ERR_LAUNCH, OK, HipLibraryError, check  # noqa: F401  (the return codes are shared)
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-HIST_LIB_PATH = os.path.join(_HERE, "csrc", "libmmvae_hist.so")
 
 HIST_ABI_VERSION = 1
 HIST_ITEM_ELEMS = 8192
@@ -40,34 +37,17 @@ HIST_PROTOTYPES = {
     "mmvae_hist_segments_f32": (_i, [_l, _p, _i, _p, _f, _i, _p, _p, _p, _p, _z, _p]),
 }
 
+BINDING = Binding("libmmvae_hist.so", "mmvae_hist.h", HIST_PROTOTYPES, "mmvae_hist_abi_version", HIST_ABI_VERSION,
+                  "mmvae_hist_build_arch")
+HIST_LIB_PATH = BINDING.path
+
 _hist: Optional[C.CDLL] = None
 
 
 def load_hist() -> C.CDLL:
-    """Load libmmvae_hist.so (built by __graft_entry__.build() / `make -C mmvae_amd/csrc`).  Raises loudly."""
+    """Load libmmvae_hist.so (see _bind.Binding.load).  Raises loudly."""
     global _hist
     if _hist is not None:
         return _hist
-    import torch  # noqa: F401  (torch's HIP runtime must be the process's: see _lib.load)
-
-    if not os.path.exists(HIST_LIB_PATH):
-        raise HipLibraryError(
-            f"{HIST_LIB_PATH} not found: build it with `make -C mmvae_amd/csrc` (or __graft_entry__.build()). "
-            "mmvae_amd has no non-HIP execution path for device tensors."
-        )
-    try:
-        lib = C.CDLL(HIST_LIB_PATH)
-    except OSError as e:  # pragma: no cover
-        raise HipLibraryError(f"could not load {HIST_LIB_PATH}: {e}") from e
-    for name, (res, args) in HIST_PROTOTYPES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise HipLibraryError(f"{HIST_LIB_PATH} does not export {name}") from e
-        fn.restype = res
-        fn.argtypes = args
-    if lib.mmvae_hist_abi_version() != HIST_ABI_VERSION:
-        raise HipLibraryError(f"{HIST_LIB_PATH} has ABI {lib.mmvae_hist_abi_version()}, this binding was written "
-                              f"against {HIST_ABI_VERSION}: rebuild it")
-    _hist = lib
-    return lib
+    _hist = BINDING.load()
+    return _hist

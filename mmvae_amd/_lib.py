@@ -9,11 +9,9 @@ import ctypes as C
 import os
 from typing import Optional
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "csrc", "libmmvae_hip.so")
-if os.environ.get("MMVAE_LIB"):  # A/B runs of two builds of the same source tree (diagnostics)
-    LIB_PATH = os.environ["MMVAE_LIB"]
+from ._bind import Binding, HipLibraryError  # noqa: F401  (HipLibraryError is part of this module's surface)
 
+ABI_VERSION = 16
 OK, ERR_ARG, ERR_LAUNCH, ERR_WORKSPACE = 0, 1, 2, 3
 _ERR_NAMES = {1: "MMVAE_ERR_ARG", 2: "MMVAE_ERR_LAUNCH", 3: "MMVAE_ERR_WORKSPACE"}
 
@@ -234,41 +232,21 @@ class AdamArenaHp(C.Structure):
                 ("beta2", _f), ("eps", _f), ("grad_scale", _f)]
 
 
-class HipLibraryError(RuntimeError):
-    pass
-
+BINDING = Binding("libmmvae_hip.so", "mmvae_hip.h", PROTOTYPES, "mmvae_abi_version", ABI_VERSION, "mmvae_build_arch")
+if os.environ.get("MMVAE_LIB"):  # A/B runs of two builds of the same source tree (diagnostics)
+    BINDING.path = os.environ["MMVAE_LIB"]
+LIB_PATH = BINDING.path
 
 _lib: Optional[C.CDLL] = None
 
 
 def load() -> C.CDLL:
-    """Load libmmvae_hip.so (built by __graft_entry__.build() / `make -C mmvae_amd/csrc`).  Raises loudly."""
+    """Load libmmvae_hip.so (see _bind.Binding.load).  ops.py calls this on every op: the cached return comes first."""
     global _lib
     if _lib is not None:
         return _lib
-    # The library works on torch's streams and device memory, so it must share torch's HIP runtime: torch ships its own
-    # libamdhip64, and whichever copy is loaded first serves the whole process.  Loading this library before torch binds
-    # its code objects to the system runtime, and every launch on a torch stream then fails (MMVAE_ERR_LAUNCH).
-    import torch  # noqa: F401
-
-    if not os.path.exists(LIB_PATH):
-        raise HipLibraryError(
-            f"{LIB_PATH} not found: build it with `make -C mmvae_amd/csrc` (or __graft_entry__.build()). "
-            "mmvae_amd has no non-HIP execution path for device tensors."
-        )
-    try:
-        lib = C.CDLL(LIB_PATH)
-    except OSError as e:  # pragma: no cover
-        raise HipLibraryError(f"could not load {LIB_PATH}: {e}") from e
-    for name, (res, args) in PROTOTYPES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise HipLibraryError(f"{LIB_PATH} does not export {name}") from e
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+    _lib = BINDING.load()
+    return _lib
 
 
 def check(rc: int, what: str) -> None:

@@ -8,13 +8,10 @@ Like `_lib`, it is the product: missing or unloadable, every call raises -- no t
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Optional
 
+from ._bind import Binding
 from ._lib import ERR_ARG, ERR_LAUNCH, OK, HipLibraryError, check  # noqa: F401  (the return codes are shared)
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-PLOT_LIB_PATH = os.path.join(_HERE, "csrc", "libmmvae_plot.so")
 
 PLOT_ABI_VERSION = 1
 PLOT_MAX_CLASSES = 16
@@ -37,37 +34,20 @@ PLOT_PROTOTYPES = {
     "mmvae_plot_composite_u8": (_i, [_p, _i, _i, _i, _p, _f, _f, _f, _f, _p, _p]),
 }
 
+BINDING = Binding("libmmvae_plot.so", "mmvae_plot.h", PLOT_PROTOTYPES, "mmvae_plot_abi_version", PLOT_ABI_VERSION,
+                  "mmvae_plot_build_arch")
+PLOT_LIB_PATH = BINDING.path
+
 _plot: Optional[C.CDLL] = None
 
 
 def load_plot() -> C.CDLL:
-    """Load libmmvae_plot.so (built by __graft_entry__.build() / `make -C mmvae_amd/csrc`).  Raises loudly."""
+    """Load libmmvae_plot.so (see _bind.Binding.load).  Raises loudly."""
     global _plot
     if _plot is not None:
         return _plot
-    import torch  # noqa: F401  (torch's HIP runtime must be the process's: see _lib.load)
-
-    if not os.path.exists(PLOT_LIB_PATH):
-        raise HipLibraryError(
-            f"{PLOT_LIB_PATH} not found: build it with `make -C mmvae_amd/csrc` (or __graft_entry__.build()). "
-            "mmvae_amd has no non-HIP execution path for device tensors."
-        )
-    try:
-        lib = C.CDLL(PLOT_LIB_PATH)
-    except OSError as e:  # pragma: no cover
-        raise HipLibraryError(f"could not load {PLOT_LIB_PATH}: {e}") from e
-    for name, (res, args) in PLOT_PROTOTYPES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise HipLibraryError(f"{PLOT_LIB_PATH} does not export {name}") from e
-        fn.restype = res
-        fn.argtypes = args
-    if lib.mmvae_plot_abi_version() != PLOT_ABI_VERSION:
-        raise HipLibraryError(f"{PLOT_LIB_PATH} has ABI {lib.mmvae_plot_abi_version()}, this binding was written "
-                              f"against {PLOT_ABI_VERSION}: rebuild it")
-    _plot = lib
-    return lib
+    _plot = BINDING.load()
+    return _plot
 
 
 def view_words(view) -> "C.Array":

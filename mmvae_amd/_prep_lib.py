@@ -8,13 +8,10 @@ product: missing or unloadable, every call raises -- no torch fallback.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Optional
 
+from ._bind import Binding
 from ._lib import ERR_ARG, ERR_LAUNCH, OK, HipLibraryError, check  # noqa: F401  (the return codes are shared)
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-PREP_LIB_PATH = os.path.join(_HERE, "csrc", "libmmvae_prep.so")
 
 PREP_ABI_VERSION = 1
 PREP_ROWS_PER_GROUP = 4
@@ -35,34 +32,17 @@ PREP_PROTOTYPES = {
     "mmvae_prep_csr_log1p_norm_i64": _NORM,
 }
 
+BINDING = Binding("libmmvae_prep.so", "mmvae_prep.h", PREP_PROTOTYPES, "mmvae_prep_abi_version", PREP_ABI_VERSION,
+                  "mmvae_prep_build_arch")
+PREP_LIB_PATH = BINDING.path
+
 _prep: Optional[C.CDLL] = None
 
 
 def load_prep() -> C.CDLL:
-    """Load libmmvae_prep.so (built by __graft_entry__.build() / `make -C mmvae_amd/csrc`).  Raises loudly."""
+    """Load libmmvae_prep.so (see _bind.Binding.load).  Raises loudly."""
     global _prep
     if _prep is not None:
         return _prep
-    import torch  # noqa: F401  (torch's HIP runtime must be the process's: see _lib.load)
-
-    if not os.path.exists(PREP_LIB_PATH):
-        raise HipLibraryError(
-            f"{PREP_LIB_PATH} not found: build it with `make -C mmvae_amd/csrc` (or __graft_entry__.build()). "
-            "mmvae_amd has no non-HIP execution path for device tensors."
-        )
-    try:
-        lib = C.CDLL(PREP_LIB_PATH)
-    except OSError as e:  # pragma: no cover
-        raise HipLibraryError(f"could not load {PREP_LIB_PATH}: {e}") from e
-    for name, (res, args) in PREP_PROTOTYPES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise HipLibraryError(f"{PREP_LIB_PATH} does not export {name}") from e
-        fn.restype = res
-        fn.argtypes = args
-    if lib.mmvae_prep_abi_version() != PREP_ABI_VERSION:
-        raise HipLibraryError(f"{PREP_LIB_PATH} has ABI {lib.mmvae_prep_abi_version()}, this binding was written "
-                              f"against {PREP_ABI_VERSION}: rebuild it")
-    _prep = lib
-    return lib
+    _prep = BINDING.load()
+    return _prep

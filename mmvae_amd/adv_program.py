@@ -19,14 +19,7 @@ from typing import Callable, List, Optional
 import torch
 
 from . import _lib
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
+from ._bind import ptr as _p, stream as _stream
 
 
 @dataclass

@@ -27,6 +27,7 @@ from __future__ import annotations
 
 import fnmatch
 import atexit
+import ctypes as C
 import os
 import pickle
 import queue
@@ -37,6 +38,8 @@ from typing import Iterator, List, Optional, Sequence, Tuple, Union
 import numpy as np
 import pandas as pd
 import torch
+
+from ._bind import CSRC, Binding
 
 
 def _wrap(v) -> List[str]:
@@ -111,6 +114,20 @@ def load_chunk(npz_path: str, metadata_path: str):
     return matrix, metadata
 
 
+_GATHER = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                      C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p])
+# name -> (restype, argtypes), in the order of include/mmvae_feed.h
+FEED_PROTOTYPES = {
+    "mmvae_feed_abi_version": (C.c_int, []),
+    "mmvae_feed_rows_nnz": (C.c_int64, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
+    "mmvae_feed_gather_rows": _GATHER,
+    "mmvae_feed_gather_rows_i32": _GATHER,
+    "mmvae_feed_cond_tables": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_void_p]),
+}
+FEED_ABI_VERSION = 3
+FEED_BINDING = Binding("libmmvae_feed.so", "mmvae_feed.h", FEED_PROTOTYPES, "mmvae_feed_abi_version", FEED_ABI_VERSION,
+                       needs_torch=False)  # host code: no build arch, and no HIP runtime to share with torch
 _FEED = None
 
 
@@ -119,29 +136,11 @@ def feed_lib():
     the HIP library; built on demand here (g++, one file) when it is missing -- it is host code, not the HIP path."""
     global _FEED
     if _FEED is None:
-        import ctypes as C
-        import subprocess
+        if not os.path.exists(FEED_BINDING.path):
+            import subprocess
 
-        here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-        path = os.path.join(here, "libmmvae_feed.so")
-        if not os.path.exists(path):
-            subprocess.run(["make", "-C", here, "libmmvae_feed.so"], check=True, capture_output=True)
-        lib = C.CDLL(path)
-        lib.mmvae_feed_rows_nnz.restype = C.c_int64
-        lib.mmvae_feed_rows_nnz.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]
-        lib.mmvae_feed_gather_rows.restype = C.c_int
-        lib.mmvae_feed_gather_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
-                                               C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
-                                               C.c_void_p]
-        lib.mmvae_feed_gather_rows_i32.restype = C.c_int
-        lib.mmvae_feed_gather_rows_i32.argtypes = lib.mmvae_feed_gather_rows.argtypes
-        lib.mmvae_feed_cond_tables.restype = C.c_int
-        lib.mmvae_feed_cond_tables.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                               C.c_void_p]
-        if lib.mmvae_feed_abi_version() != 3:
-            raise RuntimeError(f"{path} is a stale build (ABI {lib.mmvae_feed_abi_version()}, expected 3): "
-                               "make -C mmvae_amd/csrc")
-        _FEED = lib
+            subprocess.run(["make", "-C", CSRC, "libmmvae_feed.so"], check=True, capture_output=True)
+        _FEED = FEED_BINDING.load()
     return _FEED
 
 
@@ -438,8 +437,6 @@ class SpeciesChunks:
         if nnz < 0:
             raise ValueError("row index outside the chunk")
         slot.reserve(nnz)
-        import ctypes as C
-
         got = C.c_int64(0)
         if slot.index_dtype == torch.int32 and matrix.shape[1] > 0x7fffffff:
             raise ValueError("a chunk with more than 2^31 - 1 columns needs index_dtype=torch.int64")

@@ -8,6 +8,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._bind import ptr as _p, stream as _s  # noqa: F401  (the engine's modules import the two short names from here)
 from .modules.base.components import FCBlock
 
 NT, NN, TN = _lib.GEMM_NT, _lib.GEMM_NN, _lib.GEMM_TN
@@ -22,14 +23,6 @@ SLACK = _lib.GEMM_OPERAND_SLACK  # every operand the engine hands to a GEMM has 
 # one weight gradient at the reference's 60 530 genes, two per expert: 4 096 slots sent the second one (and the whole
 # gradient arena: a 93 us norm pass) back to the separate norm launch.
 SQ_FUSED_SLOTS = 8192
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _s():
-    return torch.cuda.current_stream().cuda_stream
 
 
 class _PinnedRing:

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _hist_lib
+from ._bind import stream
 from ._hist_lib import HIST_ITEM_DTYPE, HIST_ITEM_ELEMS, HIST_MAX_EDGES, HIST_STAT_NAMES, HIST_STATS
 
 _TB_EDGES: Optional[np.ndarray] = None
@@ -175,7 +176,7 @@ def segment_histograms(values: torch.Tensor, offsets: Sequence[int], lengths: Se
     out = SegmentHistograms(packed, S, e)
     rc = lib.mmvae_hist_segments_f32(n_items, items_dev.data_ptr(), S, values.data_ptr(), float(scale), e.size,
                                      edges_dev.data_ptr(), out.counts.data_ptr(), out.stats.data_ptr(), ws.data_ptr(),
-                                     ws.numel() * 8, torch.cuda.current_stream(dev).cuda_stream)
+                                     ws.numel() * 8, stream(dev))
     _hist_lib.check(rc, "mmvae_hist_segments_f32")
     out._keep = tables  # the tables outlive the launch
     return out

@@ -12,13 +12,10 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from ._bind import ptr as _ptr, stream as _stream
 from ._lib import GEMM_NT, GEMM_NN, GEMM_TN, GEMM_RELU, GEMM_ACCUMULATE, GEMM_RAW_SLABS  # noqa: F401
 
 _workspaces: dict = {}
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _chk(t: Optional[torch.Tensor], name: str, dtype=torch.float32) -> Optional[torch.Tensor]:
@@ -32,10 +29,6 @@ def _chk(t: Optional[torch.Tensor], name: str, dtype=torch.float32) -> Optional[
     if t.dtype != dtype:
         raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
     return t
-
-
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
 
 
 def _mat(t: torch.Tensor, name: str) -> Tuple[int, int, int]:
@@ -859,7 +852,7 @@ def cond_linear_bwd(dy: torch.Tensor, x: torch.Tensor, params: torch.Tensor, gra
     partials = None
     if n_red:
         need = cond_tables.partial_slots(B) * (n_in * n_out + n_out)
-        key = (x.device, torch.cuda.current_stream().cuda_stream)
+        key = (x.device, _stream())
         partials = _COND_PARTIALS.get(key)
         if partials is None or partials.numel() < need:
             partials = _COND_PARTIALS[key] = torch.empty(need, dtype=torch.float32, device=x.device)
@@ -1088,7 +1081,7 @@ def csr_log1p_normalize_(crow: torch.Tensor, values: torch.Tensor, target_sum: f
     if row_sums is not None and (row_sums.dim() != 1 or row_sums.numel() != n_rows or not row_sums.is_contiguous()):
         raise ValueError(f"csr_log1p_normalize_: row_sums must be a contiguous fp32 vector of {n_rows}")
     if stream is None:
-        stream = torch.cuda.current_stream(values.device).cuda_stream
+        stream = _stream(values.device)
     elif not isinstance(stream, int):
         stream = stream.cuda_stream
     fn = lib.mmvae_prep_csr_log1p_norm_i32 if crow.dtype == torch.int32 else lib.mmvae_prep_csr_log1p_norm_i64

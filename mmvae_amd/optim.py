@@ -21,6 +21,7 @@ import torch
 
 from . import backend, ops
 from . import dist as mdist
+from ._bind import stream
 
 
 def _pad4(n: int) -> int:
@@ -423,7 +424,7 @@ class HipAdam(torch.optim.Optimizer):
             rc = lib.mmvae_adam_step_jobs_hp(len(jobs), jobs_dev.data_ptr(), a.data.data_ptr(), a.grad.data_ptr(),
                                              a.exp_avg.data_ptr(), a.exp_avg_sq.data_ptr(), self.state_dev.data_ptr(),
                                              self.hyper_dev.data_ptr(), b1, b2, g["eps"], float(self.grad_scale),
-                                             torch.cuda.current_stream().cuda_stream)
+                                             stream())
             _lib.check(rc, "mmvae_adam_step_jobs_hp")
             self._keep_jobs = jobs_dev  # outlives the launch
         else:

@@ -27,7 +27,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import backend
+from . import _bind, backend
 from ._plot_lib import PLOT_COUNT_DEFAULT, PLOT_MAX_CLASSES, PLOT_MAX_MARKER, PLOT_MAX_SIDE
 
 FIGSIZE = (14, 8)          # the reference's plt.figure(figsize=(14, 8))
@@ -192,7 +192,7 @@ def rasterize(points: torch.Tensor, codes, n_classes: int, colors, width: int, h
     colors = colors.to(dev).contiguous()
     counts = torch.empty((n_classes, height, width), dtype=torch.int32, device=dev)
     rgba = torch.empty((height, width, 4), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    stream = _bind.stream(dev)
     _plot_lib.check(lib.mmvae_plot_count_f32(N, dims, points.data_ptr(), ld, codes.data_ptr(), n_classes, width, height,
                                              marker_px, _plot_lib.view_words(view), int(count_mode), counts.data_ptr(),
                                              stream), "mmvae_plot_count_f32")

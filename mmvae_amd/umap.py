@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import backend
+from ._bind import ptr as _ptr, stream as _stream
 
 NEGATIVE_SAMPLE_RATE = 5
 
@@ -38,14 +39,6 @@ class FuzzyGraph:
     @property
     def n(self) -> int:
         return self.indptr.numel() - 1
-
-
-def _ptr(t: torch.Tensor) -> int:
-    return t.data_ptr()
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
 
 
 # ------------------------------------------------------------------------------------------------------- 1. kNN graph

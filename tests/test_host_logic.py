@@ -162,19 +162,12 @@ def test_instantiate_reference_style_adversarial_yaml(tmp_path):
 def test_abi_header_symbols_are_exported_and_bound():
     import ctypes
     from mmvae_amd import _lib
+    from tests.abi_surface import check_surface
 
-    header = open(os.path.join(ROOT, "include", "mmvae_hip.h")).read()
-    declared = set(re.findall(r"\b(mmvae_[a-z0-9_]+)\s*\(", header))
-    declared -= {"mmvae_bn_params"}
-    lib = _lib.load()  # loads on a GPU-less host too (no compute call is made)
-    missing = [s for s in sorted(declared) if not hasattr(lib, s)]
-    assert not missing, f"declared in the header but not exported: {missing}"
-    unbound = sorted(declared - set(_lib.PROTOTYPES))
-    assert not unbound, f"declared in the header but not bound in _lib.PROTOTYPES: {unbound}"
-    extra = sorted(set(_lib.PROTOTYPES) - declared)
-    assert not extra, f"bound but not declared in the header: {extra}"
-    header_version = int(re.search(r"#define\s+MMVAE_ABI_VERSION\s+(\d+)", header).group(1))
-    assert lib.mmvae_abi_version() == header_version >= 3 and lib.mmvae_build_arch() == b"gfx950"
+    check_surface(_lib.BINDING)  # names, argument counts, version, arch, and nothing undeclared is exported
+    lib = _lib.load()
+    assert lib is _lib.BINDING.load()
+    assert lib.mmvae_abi_version() == 16 == _lib.ABI_VERSION and lib.mmvae_build_arch() == b"gfx950"
     # pure host helpers may be called without a GPU
     t, s = ctypes.c_int(), ctypes.c_int()
     assert lib.mmvae_gemm_plan(0, 512, 1024, 20000, ctypes.byref(t), ctypes.byref(s)) == 0 and s.value >= 8
@@ -186,7 +179,7 @@ def test_abi_header_symbols_are_exported_and_bound():
     assert lib.mmvae_gemm_set_precision(_lib.GEMM_PRECISION_BF16X3) == 0
 
 
-def test_abi_structs_have_the_librarys_layout_and_nothing_undeclared_is_exported():
+def test_abi_structs_have_the_librarys_layout():
     import ctypes
     from mmvae_amd import _lib
 
@@ -194,15 +187,21 @@ def test_abi_structs_have_the_librarys_layout_and_nothing_undeclared_is_exported
     assert ctypes.sizeof(_lib.Planes) == lib.mmvae_sizeof_planes() == 24
     assert ctypes.sizeof(_lib.ReconArgs) == lib.mmvae_sizeof_recon_args()
     assert ctypes.sizeof(_lib.SplitJob) == lib.mmvae_sizeof_split_job()
-    # a retired entry point is gone from the library too: it exports no mmvae_* symbol that the header does not declare
-    # (candidates: every such name in the file's string tables; exported: the loader resolves it)
-    header = open(os.path.join(ROOT, "include", "mmvae_hip.h")).read()
-    declared = set(re.findall(r"\b(mmvae_[a-z0-9_]+)\s*\(", header))
-    image = open(_lib.LIB_PATH, "rb").read()
-    names = {m.decode() for m in re.findall(rb"(?<![A-Za-z0-9_])mmvae_[a-z0-9_]+(?=\x00)", image)}
-    assert declared - {"mmvae_bn_params"} <= names, "the scan of the string tables misses exported names"
-    stale = sorted(n for n in names - declared if hasattr(lib, n))
-    assert not stale, f"exported but not declared in the header: {stale}"
+
+
+def test_a_library_of_another_abi_version_is_refused():
+    """The check that the training library shares with the satellites since it loads through the same Binding: a
+    binding written against another version than the library's refuses to load it and names both numbers."""
+    from mmvae_amd import _lib, _stats_lib
+    from mmvae_amd._bind import Binding
+
+    assert _stats_lib.load_stats().mmvae_stats_abi_version() == 1
+    stale = Binding("libmmvae_stats.so", "mmvae_stats.h", _stats_lib.STATS_PROTOTYPES, "mmvae_stats_abi_version", 7,
+                    "mmvae_stats_build_arch")
+    with pytest.raises(_lib.HipLibraryError, match=r"has ABI 1, this binding was written against 7: rebuild it"):
+        stale.load()
+    with pytest.raises(_lib.HipLibraryError):  # a refused library is not cached
+        stale.load()
 
 
 def _host_block():

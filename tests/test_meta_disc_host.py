@@ -11,32 +11,19 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from tests.abi_surface import check_surface
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mmvae_disc.h")
 NAMES = {"mmvae_disc_abi_version", "mmvae_disc_build_arch", "mmvae_disc_tail_workspace_bytes", "mmvae_disc_tail_f32"}
-
-
-def _declared(header: str) -> dict:
-    """name -> argument count of every mmvae_disc_* function the header declares."""
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(mmvae_disc_\w+)\s*\(([^;{]*?)\)\s*;", code, re.S):
-        args = [a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"]
-        out[m.group(1)] = len(args)
-    return out
 
 
 def test_header_symbols_are_exported_and_bound():
     from mmvae_amd import _disc_lib
 
     header = open(HEADER).read()
-    declared = _declared(header)
-    assert set(declared) == NAMES
-    lib = _disc_lib.load_disc()  # loads on a GPU-less host too (no compute call is made)
-    assert set(_disc_lib.DISC_PROTOTYPES) == set(declared)
-    for name, n_args in declared.items():
-        assert hasattr(lib, name), name
-        assert len(_disc_lib.DISC_PROTOTYPES[name][1]) == n_args, name
+    declared = check_surface(_disc_lib.BINDING)
+    assert set(declared) == NAMES == set(_disc_lib.DISC_PROTOTYPES)
     assert declared["mmvae_disc_tail_f32"] == 22
     for word in ("MAX_H1", "MAX_H2", "MAX_W2", "TILE_ROWS", "GRID_CAP"):
         value = int(re.search(r"#define\s+MMVAE_DISC_" + word + r"\s+(\d+)", header).group(1))
