@@ -81,10 +81,44 @@ class Lookahead:
                 withdraw() if withdraw is not None else self.model.hint_next_batch(None)
 
 
+class _SkipFirst:
+    """`batches` without its first `n` (a resumed epoch: what the interrupted run had already consumed is drawn and
+    dropped, so that the modality draws and the loaders stand where they stood)."""
+
+    def __init__(self, batches: Iterable, n: int):
+        self.batches, self.n = batches, n
+
+    def __iter__(self) -> Iterator:
+        it = iter(self.batches)
+        for _ in range(self.n):
+            if next(it, None) is None:
+                return
+        yield from it
+
+
+def _epoch_source(batches) -> Optional[MultiModalBatches]:
+    """The MultiModalBatches behind `batches` (itself, or wrapped in a Prefetcher / Lookahead): its `epoch` seeds the
+    modality draws, so a checkpoint records it."""
+    for _ in range(4):
+        if isinstance(batches, MultiModalBatches):
+            return batches
+        batches = getattr(batches, "batches", None)
+        if batches is None:
+            break
+    return None
+
+
 class Trainer:
     def __init__(self, max_epochs: int = 10, max_steps: int = -1, limit_train_batches: Optional[int] = None,
                  limit_val_batches: Optional[int] = None, check_val_every_n_epoch: int = 1,
-                 num_sanity_val_steps: int = 0, **unused):
+                 num_sanity_val_steps: int = 0, callbacks: Optional[list] = None, default_root_dir: Optional[str] = None,
+                 enable_checkpointing: bool = True, **unused):
+        """callbacks: `mmvae_amd.callbacks.ModelCheckpoint` / `EarlyStopping` objects (at most one ModelCheckpoint); with
+        none, fit() does what it did before there were any.  default_root_dir: where a ModelCheckpoint without a dirpath
+        puts `checkpoints/`.  enable_checkpointing=False with a ModelCheckpoint among the callbacks raises, as in
+        Lightning."""
+        from .callbacks import EarlyStopping, ModelCheckpoint
+
         self.max_epochs = max_epochs
         self.max_steps = max_steps
         self.limit_train_batches = limit_train_batches
@@ -93,48 +127,203 @@ class Trainer:
         self.num_sanity_val_steps = num_sanity_val_steps
         self.global_step = 0
         self.history: List[dict] = []
+        self.callbacks = list(callbacks or [])
+        self.default_root_dir = default_root_dir
+        self.enable_checkpointing = enable_checkpointing
+        ckpts = [c for c in self.callbacks if isinstance(c, ModelCheckpoint)]
+        if len(ckpts) > 1:
+            raise ValueError("Trainer: one ModelCheckpoint at most (a second one would need a second snapshot buffer)")
+        if ckpts and not enable_checkpointing:
+            raise ValueError("Trainer: enable_checkpointing=False, but a ModelCheckpoint is among the callbacks")
+        self.checkpoint_callback = ckpts[0] if ckpts else None
+        self.early_stopping_callbacks = [c for c in self.callbacks if isinstance(c, EarlyStopping)]
+        self.callback_metrics: Dict[str, float] = {}  # what the callbacks monitor (mmvae_amd.callbacks)
+        self.current_epoch = 0
+        self.should_stop = False
+        self.stop_reason: Optional[str] = None
+        self.checkpointer = None  # mmvae_amd.checkpoint.Checkpointer of the model being fitted
+        self._pending = None  # the save in flight
+        self._diverged = False  # a snapshot found non-finite values: nothing more is written
+        self._resume: Optional[dict] = None  # position in the data a loaded checkpoint asks fit() to take up
 
     @classmethod
     def from_yaml(cls, path: str) -> "Trainer":
+        from .callbacks import from_yaml_list
+
         with open(path) as f:
             cfg = yaml.safe_load(f) or {}
         keys = ("max_epochs", "max_steps", "limit_train_batches", "limit_val_batches", "check_val_every_n_epoch",
-                "num_sanity_val_steps")
-        return cls(**{k: cfg[k] for k in keys if cfg.get(k) is not None})
+                "num_sanity_val_steps", "default_root_dir", "enable_checkpointing")
+        kw = {k: cfg[k] for k in keys if cfg.get(k) is not None}
+        if cfg.get("callbacks"):
+            kw["callbacks"] = from_yaml_list(cfg["callbacks"])
+        return cls(**kw)
 
     def _snapshot(self, model) -> dict:
         return {k: (float(v.detach()) if torch.is_tensor(v) else v) for k, v in model.logged.items()}
 
-    def fit(self, model, train_batches: Iterable, val_batches: Optional[Iterable] = None):
+    def fit(self, model, train_batches: Iterable, val_batches: Optional[Iterable] = None,
+            ckpt_path: Optional[str] = None):
+        """ckpt_path: a file written by this Trainer's ModelCheckpoint (mmvae_amd.checkpoint): the model, the optimisers,
+        the random state, `global_step`, the epoch, the callbacks' state and `history` are restored and the run goes on
+        where the file was written -- for a mid-epoch file behind the batches that epoch had already consumed.  With
+        callbacks, `stop_reason` says afterwards why the run ended early (None: it did not), and the last checkpoint
+        write has finished when fit() returns."""
         model.optimizers()
         stub = model.trainer
-        for epoch in range(self.max_epochs):
+        self.should_stop, self.stop_reason, self._diverged = False, None, False
+        if self.checkpoint_callback is not None and self.checkpointer is None:
+            from .checkpoint import Checkpointer
+
+            self.checkpointer = Checkpointer(model)  # (buffers and job table: once, before the first captured step)
+        if ckpt_path is not None:
+            from .checkpoint import load
+
+            load(ckpt_path, model, trainer=self)
+            stub.global_step = self.global_step
+        resume, self._resume = self._resume or {}, None
+        source, val_source = _epoch_source(train_batches), _epoch_source(val_batches)
+        if source is not None and resume.get("batches_epoch") is not None:
+            source.epoch = resume["batches_epoch"]
+        if val_source is not None and resume.get("val_batches_epoch") is not None:
+            val_source.epoch = resume["val_batches_epoch"]
+        skip = int(resume.get("batches_consumed") or 0)
+        for epoch in range(int(resume.get("next_epoch") or 0), self.max_epochs):
+            self.current_epoch = epoch
+            seed_epoch = source.epoch if source is not None else None  # (what this epoch's modality draws are seeded with)
             model.train()
             stub.set_stage("training")
-            for i, batch in enumerate(Lookahead(train_batches, model) if hasattr(model, "hint_next_batch") else train_batches):
+            batches = _SkipFirst(train_batches, skip) if skip else train_batches
+            for i, batch in enumerate(Lookahead(batches, model) if hasattr(model, "hint_next_batch") else batches, start=skip):
                 if self.limit_train_batches is not None and i >= self.limit_train_batches:
                     break
                 model.training_step(batch, i)
                 self.global_step += 1
                 stub.global_step = self.global_step
+                if self.checkpoint_callback is not None:
+                    paths = self.checkpoint_callback.on_train_step(self)
+                    if paths:
+                        self._save(model, paths, epoch, {"next_epoch": epoch, "batches_consumed": i + 1,
+                                                         "batches_epoch": seed_epoch,
+                                                         "val_batches_epoch": getattr(val_source, "epoch", None)})
+                    if self._pending is not None and self._pending.done():
+                        self._settle_pending()  # (a finished write: a refusal for non-finite values ends the run here)
+                    if self.should_stop:
+                        break
                 if 0 < self.max_steps <= self.global_step:
                     break
+            skip = 0
             self.history.append({"epoch": epoch, "stage": "training", **self._snapshot(model)})
-            if val_batches is not None and (epoch + 1) % self.check_val_every_n_epoch == 0:
+            if self.callbacks:
+                self.callback_metrics.update({k: v for k, v in self.history[-1].items() if isinstance(v, float)})
+                self._epoch_callbacks(model, epoch, seed_epoch, val_source, train_epoch_end=True)
+                if val_batches is None:  # (no validation: its callbacks act on the training epoch's values, as in Lightning)
+                    self._epoch_callbacks(model, epoch, seed_epoch, val_source, train_epoch_end=False)
+            if val_batches is not None and (epoch + 1) % self.check_val_every_n_epoch == 0 and not self.should_stop:
                 self.validate(model, val_batches)
-            if 0 < self.max_steps <= self.global_step:
+                if self.callbacks:
+                    self._epoch_callbacks(model, epoch, seed_epoch, val_source, train_epoch_end=False)
+            if 0 < self.max_steps <= self.global_step or self.should_stop:
                 break
+        self._finish_saves()
         return self.history
+
+    # ------------------------------------------------------------------------------------------------- callbacks
+    def _epoch_callbacks(self, model, epoch: int, seed_epoch, val_source, train_epoch_end: bool) -> None:
+        """Behind a training epoch / a validation: the early-stopping checks, then the checkpoint the ModelCheckpoint asks
+        for (Lightning's order: the file holds the early-stopping state of the check just made; the epoch that stops the
+        run is still saved)."""
+        position = {"next_epoch": epoch + 1, "batches_consumed": 0,
+                    "batches_epoch": None if seed_epoch is None else seed_epoch + 1,
+                    "val_batches_epoch": getattr(val_source, "epoch", None)}
+        for stopper in self.early_stopping_callbacks:
+            if stopper.check_on_train_epoch_end == train_epoch_end:
+                reason = stopper.check(self, epoch)
+                if reason is not None:
+                    self.should_stop, self.stop_reason = True, self.stop_reason or reason
+        if self.checkpoint_callback is not None:
+            paths = self.checkpoint_callback.on_epoch_trigger(self, epoch, train_epoch_end)
+            if paths:
+                self._save(model, paths, epoch, position)
+
+    def _save(self, model, paths: List[str], epoch: int, position: dict) -> None:
+        """One snapshot into every path of `paths`.  The save before it is looked at first: had it found non-finite
+        values, its files were left as they were, the run stops and nothing more is written."""
+        if self._settle_pending():
+            return
+        extra = {"epoch": epoch, "global_step": self.global_step,
+                 "callbacks": {c.state_key: c.state_dict() for c in self.callbacks},
+                 "mmvae_amd": {**position, "history": self.history}}
+        self._pending = self.checkpointer.save(paths[0], extra, also=paths[1:])
+
+    def _settle_pending(self) -> bool:
+        """Wait for the save in flight (its error is raised here).  True when it refused to write: non-finite values."""
+        pending, self._pending = self._pending, None
+        if pending is None:
+            return self._diverged
+        pending.wait()
+        if pending.nonfinite:
+            self.should_stop = self._diverged = True
+            self.stop_reason = (f"checkpoint not written: non-finite values in {sorted(pending.nonfinite)} "
+                                f"(global step {self.global_step})")
+            return True
+        return False
+
+    def _finish_saves(self) -> None:
+        self._settle_pending()
+        if self.checkpointer is not None:
+            self.checkpointer.wait()
+
+    def _resume_from(self, ckpt: dict) -> None:
+        """mmvae_amd.checkpoint.load(..., trainer=self): take up the file's position."""
+        own = ckpt["mmvae_amd"]
+        self.global_step = int(ckpt["global_step"])
+        self.current_epoch = int(own.get("next_epoch") or 0)
+        self.history = list(own.get("history") or [])
+        states = ckpt.get("callbacks") or {}
+        for c in self.callbacks:
+            if c.state_key in states:
+                c.load_state_dict(states[c.state_key])
+        self._resume = {k: own.get(k) for k in ("next_epoch", "batches_consumed", "batches_epoch", "val_batches_epoch")}
 
     @torch.no_grad()
     def validate(self, model, batches: Iterable):
         model.eval()
         model.trainer.set_stage("validation")
+        sums: dict = {}
         for i, batch in enumerate(batches):
             if self.limit_val_batches is not None and i >= self.limit_val_batches:
                 break
             model.validation_step(batch, i)
+            if self.callbacks:
+                self._accumulate(model, batch, sums)
         self.history.append({"stage": "validation", **self._snapshot(model)})
+        if self.callbacks:
+            self._reduce(sums)
+
+    @staticmethod
+    def _accumulate(model, batch, sums: dict) -> None:
+        """The scalars this validation step logged (`.../validation/<expert>` and `val_loss`), times the batch's rows,
+        added to the epoch's sums where they are: device scalars stay on the device, nothing is read here."""
+        rows = int(batch[0].shape[0])
+        suffix = f"/validation/{batch[2]}"
+        for key, v in model.logged.items():
+            if not (key.endswith(suffix) or key == "val_loss"):
+                continue
+            term = v.detach() * rows if torch.is_tensor(v) else float(v) * rows
+            held = sums.get(key)
+            sums[key] = (term, rows) if held is None else (held[0] + term, held[1] + rows)
+
+    def _reduce(self, sums: dict) -> None:
+        """Row-weighted epoch means -> callback_metrics, with ONE read of the device sums."""
+        on_device = [k for k, (t, _) in sums.items() if torch.is_tensor(t)]
+        if on_device:
+            host = torch.stack([sums[k][0].reshape(()).float() for k in on_device]).cpu().tolist()
+            for k, v in zip(on_device, host):
+                self.callback_metrics[k] = v / sums[k][1]
+        for k, (t, rows) in sums.items():
+            if not torch.is_tensor(t):
+                self.callback_metrics[k] = t / rows
 
     @torch.no_grad()
     def predict(self, model, batches: Iterable, writer=None) -> list:
