@@ -386,6 +386,24 @@ class Trainer:
                 for category in categories]
 
     @torch.no_grad()
+    def integration_metrics(self, model, batches: Iterable, **kw):
+        """`mmvae_amd.mixing.integration_metrics` of the latent embeddings: `predict_step` over the batches with z kept
+        where it was produced, the batches' metadata frames stacked (one row per cell, with the "species" column
+        predict_step adds -- the default batch column), then LISI of the batch and label columns and the label transfer
+        across the batches on the exact kNN graph of z.  `kw`: batch_key, label_keys, n_neighbors, perplexity, transfer."""
+        import pandas as pd
+
+        from .constants import REGISTRY_KEYS as RK
+        from .mixing import integration_metrics
+
+        outs = [p[RK.Z] for p in self.predict(model, batches)]
+        if not outs:
+            raise ValueError("Trainer.integration_metrics: no batches")
+        z = torch.cat([o[0] for o in outs], 0)
+        metadata = pd.concat([o[1] for o in outs], ignore_index=True)
+        return integration_metrics(z, metadata, **kw)
+
+    @torch.no_grad()
     def correlations(self, model, groups: Iterable, decimals: Optional[int] = 3):
         """The table of get_correlations (runners/run_correlations.py:95-145) as a pandas.DataFrame, one row per group of
         `groups` = (group_id, batch_a, batch_b) with the two batches of different experts
