@@ -18,7 +18,7 @@ INCLUDE = os.path.join(os.path.dirname(_PACKAGE), "include")
 # the modules that hold a device library's BINDING (a new library: one prototypes module, one Makefile line, one entry
 # here); __graft_entry__.build() loads each and checks its version and build arch
 DEVICE_LIBRARY_MODULES = ("_lib", "_stats_lib", "_disc_lib", "_umap_lib", "_hist_lib", "_prep_lib", "_plot_lib",
-                          "_ckpt_lib", "_mix_lib")
+                          "_ckpt_lib", "_mix_lib", "_sil_lib")
 
 
 class HipLibraryError(RuntimeError):

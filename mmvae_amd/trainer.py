@@ -404,6 +404,23 @@ class Trainer:
         return integration_metrics(z, metadata, **kw)
 
     @torch.no_grad()
+    def silhouette_widths(self, model, batches: Iterable, **kw):
+        """`mmvae_amd.silhouette.silhouette_widths` of the latent embeddings: z and the metadata gathered exactly as
+        `integration_metrics` gathers them, then the label silhouette of every label column and the batch silhouette
+        inside its classes, over all cells.  `kw`: batch_key, label_keys, metric."""
+        import pandas as pd
+
+        from .constants import REGISTRY_KEYS as RK
+        from .silhouette import silhouette_widths
+
+        outs = [p[RK.Z] for p in self.predict(model, batches)]
+        if not outs:
+            raise ValueError("Trainer.silhouette_widths: no batches")
+        z = torch.cat([o[0] for o in outs], 0)
+        metadata = pd.concat([o[1] for o in outs], ignore_index=True)
+        return silhouette_widths(z, metadata, **kw)
+
+    @torch.no_grad()
     def correlations(self, model, groups: Iterable, decimals: Optional[int] = 3):
         """The table of get_correlations (runners/run_correlations.py:95-145) as a pandas.DataFrame, one row per group of
         `groups` = (group_id, batch_a, batch_b) with the two batches of different experts
