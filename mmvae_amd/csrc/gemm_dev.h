@@ -197,7 +197,7 @@ __device__ __forceinline__ void x3_pack4_lean(f32x2 lo, f32x2 hi, uint2 (&pk)[3]
 template <int BM, int BN, int WGM, int WGN, int EPI, int TM, int TN, bool MF16 = false>
 __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const GemmArgs& g, int bm, int bn, int z,
                                               float* lds) {
-    static_assert(!MF16 || EPI == EPI_STD || EPI == EPI_RECON, "16x16 accumulator layout: standard and reconstruction epilogues");
+    static_assert(!MF16 || EPI == EPI_STD, "16x16 accumulator layout: the standard epilogue (reconstruction: recon_lds_epilogue)");
     constexpr int WTM = BM / WGM, WTN = BN / WGN;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -315,126 +315,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const GemmA
     } else {
         // bias + ReLU + squared error + dP; per-cell SE reduced over the 32 lanes that share a row.
         float* rowsum = lds;  // [WGN][BM] scratch: the operand tiles are dead after the final barrier
-        if constexpr (MF16) {
-            // 16x16x32 accumulators (16-byte path only: the launcher of the fused kernel sets c_vec).  Registers
-            // 4 gq .. 4 gq + 3 of a 32x32 block are sub-block (si, sj) = (gq >> 1, gq & 1): rows 16 si + 4 (lane >> 4) + j,
-            // column 16 sj + (lane & 15); after the quad transpose a lane holds row 16 si + 4 (lane >> 4) + q and the four
-            // columns 16 sj + (lane & 12) .. + 3.  Column groups outermost (one bias vector and one column-sum vector
-            // live at a time), the per-row squared errors of the wave's 2 TM row groups in 2 TM scalars.
-            const int q = lane & 3, lg = lane >> 4, c12 = lane & 12;
-            const bool odd = q & 1, hi = q & 2;
-            float sr[TM][2];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) sr[i][0] = sr[i][1] = 0.f;
-            float* colbuf = lds + WGN * BM;  // [WGM][BN], behind the row sums
-#pragma unroll
-            for (int n = 0; n < TN; ++n) {
-#pragma unroll
-                for (int sj = 0; sj < 2; ++sj) {
-                    const int cloc = wn * WTN + n * 32 + 16 * sj + c12;
-                    const int col = bn * BN + cloc;
-                    f32x4 bn4 = {0.f, 0.f, 0.f, 0.f};
-                    if (g.bias && col < g.N) {
-                        if (col + 3 < g.N) {
-                            bn4 = *reinterpret_cast<const f32x4*>(g.bias + col);
-                        } else {
-                            for (int j = 0; j < g.N - col; ++j) bn4[j] = g.bias[col + j];
-                        }
-                    }
-                    f32x4 csum = {0.f, 0.f, 0.f, 0.f};
-                    // the x rows of this column group's 2 TM row groups, requested together (clamped addresses: no
-                    // branch around the loads) -- one load at a time cost a memory round trip per 16 x 16 sub-block, 40
-                    // in a row per 256 x 160 tile (C3: 3.53 -> 3.455 ms; requested one column group AHEAD instead: more
-                    // spills, 3.79 against 3.72)
-                    f32x4 xpre[TM][2];
-                    const bool col_whole = col + 3 < g.N;
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int si = 0; si < 2; ++si) {
-                            const int row = bm * BM + wm * WTM + i * 32 + 16 * si + 4 * lg + q;
-                            const int xr = min(row, g.M - 1) % g.x_rows;
-                            xpre[i][si] = *reinterpret_cast<const f32x4*>(g.x + (int64_t)xr * g.ldx + (col_whole ? col : 0));
-                        }
-#pragma unroll
-                    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-                        for (int si = 0; si < 2; ++si) {
-                            const int gq = 2 * si + sj;
-                            const float a0 = acc[i][n][4 * gq], a1 = acc[i][n][4 * gq + 1], a2 = acc[i][n][4 * gq + 2],
-                                        a3 = acc[i][n][4 * gq + 3];
-                            const float r0 = quad_perm<1, 0, 3, 2>(odd ? a0 : a1), r1 = quad_perm<1, 0, 3, 2>(odd ? a2 : a3);
-                            const float c0 = odd ? r0 : a0, c1 = odd ? a1 : r0, c2 = odd ? r1 : a2, c3 = odd ? a3 : r1;
-                            const float t0 = quad_perm<2, 3, 0, 1>(hi ? c0 : c2), t1 = quad_perm<2, 3, 0, 1>(hi ? c1 : c3);
-                            f32x4 p;
-                            p[0] = hi ? t0 : c0;
-                            p[1] = hi ? t1 : c1;
-                            p[2] = hi ? c2 : t0;
-                            p[3] = hi ? c3 : t1;
-                            const int row = bm * BM + wm * WTM + i * 32 + 16 * si + 4 * lg + q;
-                            const int xr = row % g.x_rows;
-                            if (row < g.M && col + 3 < g.N) {
-                                p += bn4;
-                                const f32x4 xv = xpre[i][si];
-                                f32x4 xh, dp;
-#pragma unroll
-                                for (int j = 0; j < 4; ++j) {
-                                    xh[j] = fmaxf(p[j], 0.f);
-                                    const float d = xh[j] - xv[j];
-                                    sr[i][si] += d * d;
-                                    dp[j] = (p[j] > 0.f) ? 2.f * d : 0.f;
-                                }
-                                if (g.xhat) *reinterpret_cast<f32x4*>(g.xhat + (int64_t)row * g.ldxhat + col) = xh;
-                                if (g.dP) *reinterpret_cast<f32x4*>(g.dP + (int64_t)row * g.lddp + col) = dp;
-                                if (g.dPp) {
-                                    uint2 pk[3];
-                                    x3_pack4_lean(f32x2{dp[0], dp[1]}, f32x2{dp[2], dp[3]}, pk);
-                                    unsigned short* pp = g.dPp + (int64_t)row * g.lddpp + col;
-#pragma unroll
-                                    for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<uint2*>(pp + pl * g.dp_pstride) = pk[pl];
-                                }
-                                csum += dp;
-                            } else if (row < g.M && col < g.N) {  // G % 4 != 0: the group straddling the edge
-                                p += bn4;
-                                for (int j = 0; j < g.N - col; ++j) {
-                                    const float xhj = fmaxf(p[j], 0.f);
-                                    const float d = xhj - g.x[(int64_t)xr * g.ldx + col + j];
-                                    sr[i][si] += d * d;
-                                    const float dpj = (p[j] > 0.f) ? 2.f * d : 0.f;
-                                    if (g.xhat) g.xhat[(int64_t)row * g.ldxhat + col + j] = xhj;
-                                    if (g.dP) g.dP[(int64_t)row * g.lddp + col + j] = dpj;
-                                    csum[j] += dpj;
-                                }
-                            }
-                        }
-                    }
-                    if (g.col_part) {  // the 16 lanes that share this column group (q, lane >> 4) -> one, per wave
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            float v = csum[j];
-                            v += __shfl_xor(v, 1, 64);
-                            v += __shfl_xor(v, 2, 64);
-                            v += __shfl_xor(v, 16, 64);
-                            v += __shfl_xor(v, 32, 64);
-                            csum[j] = v;
-                        }
-                        if (q == 0 && lg == 0) {
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) colbuf[wm * BN + cloc + j] = csum[j];
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int si = 0; si < 2; ++si) {
-                    float v = sr[i][si];  // the 4 lanes of a row (lane & 12) -> one
-                    v += __shfl_xor(v, 4, 64);
-                    v += __shfl_xor(v, 8, 64);
-                    if (c12 == 0) rowsum[wn * BM + wm * WTM + i * 32 + 16 * si + 4 * lg + q] = v;
-                }
-        } else if (g.c_vec) {
+        if (g.c_vec) {
             // 16-byte path (x, xhat, dP 16-byte regular): quad transpose as in the standard epilogue, so that x is
             // read and xhat / dP are written as one row x 4 genes per lane; the row's SE is then the sum over the 8
             // lanes of a half that share q = lane & 3 (strides 4, 8, 16).
@@ -1265,6 +1146,221 @@ struct XwPlanes {
     }
 };
 
+// ---- reconstruction epilogue of the wave-specialised kernel (16x16 accumulators): all 512 threads, from LDS.
+// Behind an item's last k-tile barrier the image the multipliers worked on is dead; the OTHER image already holds the
+// first k-tile of the workgroup's next item (the stagers run ahead across items), so one image is what there is: the
+// accumulators leave the registers as four slices of 64 rows, one slice in LDS at a time.
+//   slice [64][BN + 4] fp32   the +4 puts the rows of one ds_write_b32 (4 apart) 16 banks apart
+//   colp  [16][BN]            per-task column sums of dP over the rows of one multiplier wave
+//   colw  [WGM][BN]           the column sums per multiplier wave
+//   bias  [BN]                this column tile's bias (zeros beyond N or without a bias)
+// Element work: a thread owns one 4-gene group (BN / 4 threads cover a row: 640 / 512 contiguous bytes of x, xhat, dP)
+// of the rows r0, r0 + 16, r0 + 32, r0 + 48 of the slice -- a "task"; 16 BN / 4 tasks per slice, so on the 160-wide tile
+// the first 128 stager threads take a second one.  It writes d = xhat - x back over the accumulator values it read.
+// The two partial sums are then formed EXACTLY as the register epilogue formed them, so that se_part and col_part keep
+// their bits (sequential training steps amplify a last-bit difference about ten-fold per step):
+//   se_part: per row four chains over the 16-column groups of a multiplier wave's columns, lane c of a quad taking
+//       columns 16 g + 4 c .. + 3 in order, s + d * d as a multiply and an add (a fused multiply-add for the elements of
+//       the group that straddles N: the element path); (chain 0 + chain 1) + (chain 2 + chain 3); the waves along N in order.
+//   col_part: a task IS the register epilogue's chain of one lane -- rows 16 apart, plain adds -- as long as the rows are
+//       those of one multiplier wave (WTM rows: the sum is carried over the wave's slices); the 16 chains of a column
+//       as a binary tree in row order; the waves of a 128-row half in order.
+template <int BM, int BN, int WGM, int WGN>
+struct ReconLds {
+    static constexpr int THREADS = 2 * NT;
+    static constexpr int SLICE = 64, NSL = BM / SLICE;
+    static constexpr int RS = BN + 4;                        // floats per slice row
+    static constexpr int CG = BN / 4;                        // 4-gene groups (= threads) per row
+    static constexpr int BAND = 16, KROWS = SLICE / BAND;    // rows of a task are BAND apart, KROWS per slice
+    static constexpr int TASKS = BAND * CG;                  // per slice
+    static constexpr int NTASK = (TASKS + THREADS - 1) / THREADS;  // per thread
+    static constexpr int WTM = BM / WGM, WTN = BN / WGN;     // a multiplier wave's share of the tile
+    static constexpr int SPU = WTM / SLICE;                  // slices per multiplier wave along M
+    static constexpr int HALVES = BM / 128, WPH = WGM / HALVES;
+    static constexpr int COLP_OFF = SLICE * RS * 4;
+    static constexpr int COLW_OFF = COLP_OFF + BAND * BN * 4;
+    static constexpr int BIAS_OFF = COLW_OFF + WGM * BN * 4;
+    static constexpr int BYTES = BIAS_OFF + BN * 4;
+    // workgroup barriers of one item's epilogue: behind the dump, the element work and the sums of every slice.  Both
+    // roles of the kernel run recon_lds_epilogue itself, so they cannot disagree on it.
+    static constexpr int BARRIERS = 3 * NSL;
+    static_assert(BM % 128 == 0 && WTM % SLICE == 0 && WTN % 16 == 0 && RS % 16 == 4, "slice geometry");
+    static_assert(NTASK == 1 || SPU == 1, "a column chain carried over slices belongs to one task");
+    static_assert(COLP_OFF % 16 == 0 && BN <= NT, "16-byte slice rows; one stager thread per column");
+    static_assert(NTASK <= 2 && TASKS - THREADS <= NT, "the tasks beyond one per thread go to the stager threads");
+};
+
+// `buf`: the dead image.  dump(sl): the caller's accumulators of slice sl -> buf (the multiplier waves that hold them;
+// a no-op in the stagers).  Contains every barrier of the epilogue, the final one included.
+// STAGER: the caller's role (a compile-time fact, so the multipliers' copy holds no code of the stagers' share).
+template <int BM, int BN, int WGM, int WGN, bool STAGER, class Dump>
+__device__ __forceinline__ void recon_lds_epilogue(const GemmArgs& g, int bm, int bn, char* buf, Dump&& dump) {
+    using P = ReconLds<BM, BN, WGM, WGN>;
+    // Everything per-thread is derived HERE, behind the main loop: an opaque copy of the thread id keeps the compiler
+    // from hoisting the invariants over the loop, where every register is taken (the spills of the earlier epilogue).
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    float* slice = reinterpret_cast<float*>(buf);
+    float* colp = reinterpret_cast<float*>(buf + P::COLP_OFF);
+    float* colw = reinterpret_cast<float*>(buf + P::COLW_OFF);
+    float* biasl = reinterpret_cast<float*>(buf + P::BIAS_OFF);
+    const int rt = tid - NT;  // >= 0: a stager thread
+    // The x rows are requested NSETS passes ahead -- across the slices' barriers too -- through NSETS register sets; pass
+    // (task ti, row k) uses set k % NSETS and issues the next request into it as soon as it has used it (two sets on the
+    // 160-wide tile: four do not fit beside its 160 accumulator registers).  The wait in front of
+    // a pass then leaves the younger requests, and the stores issued between them, outstanding; nothing is handed from
+    // one set to another (a copy would wait for the youngest request).  x row = output row % x_rows: always inside x; a
+    // thread without four whole columns (or without a second task) requests a group nobody uses.
+    auto x_request = [&](int sl, int ti, int k) __attribute__((always_inline)) {
+        const int task = ti == 0 ? tid : P::THREADS + rt;
+        const int t2 = task < P::TASKS ? task : tid;
+        const int col = bn * BN + 4 * (t2 % P::CG);
+        const unsigned xr = (unsigned)(bm * BM + sl * P::SLICE + t2 / P::CG + P::BAND * k) % (unsigned)g.x_rows;
+        return *reinterpret_cast<const f32x4*>(g.x + (int64_t)xr * g.ldx + (col + 3 < g.N ? col : 0));
+    };
+    // a second task (the 160-wide tile has 640 for 512 threads) goes to the first stager threads: they have the
+    // registers for it, the multipliers beside their accumulators have not
+    constexpr int NTASK = STAGER ? P::NTASK : 1;
+    constexpr int NSETS = P::KROWS, NPASS = NTASK * P::KROWS;
+    static_assert(P::KROWS % NSETS == 0, "a pass finds its set by its row index");
+    f32x4 xs[NSETS];
+#pragma unroll
+    for (int k = 0; k < NSETS; ++k) xs[k] = x_request(0, 0, k);
+    if (tid < BN) {
+        const int col = bn * BN + tid;
+        biasl[tid] = (g.bias && col < g.N) ? g.bias[col] : 0.f;
+    }
+#pragma unroll 1
+    for (int sl = 0; sl < P::NSL; ++sl) {
+        dump(sl);
+        __syncthreads();
+        const bool unit_end = (sl % P::SPU) == P::SPU - 1;  // the last slice of a multiplier wave's rows
+#pragma unroll
+        for (int ti = 0; ti < NTASK; ++ti) {
+            const int task = ti == 0 ? tid : P::THREADS + rt;
+            const bool on = task < P::TASKS;
+            const int cg = task % P::CG, r0 = task / P::CG;
+            const int col = bn * BN + 4 * cg;
+            const bool whole = col + 3 < g.N, edge = !whole && col < g.N;  // (G % 4 != 0: the group straddling the edge)
+#pragma unroll
+            for (int k = 0; k < P::KROWS; ++k) {
+                const f32x4 xv = xs[k % NSETS];
+                if (on) {
+                    const int r = r0 + P::BAND * k;
+                    const int row = bm * BM + sl * P::SLICE + r;
+                    float* ps = slice + r * P::RS + 4 * cg;
+                    f32x4 p = *reinterpret_cast<const f32x4*>(ps);
+                    const f32x4 bn4 = *reinterpret_cast<const f32x4*>(biasl + 4 * cg);
+                    f32x4 dd = {0.f, 0.f, 0.f, 0.f};
+                    // the task's column chain lives in colp (beside 160 accumulator registers it does not fit): begun
+                    // with the first row of a multiplier wave's rows, complete with the last
+                    float* cpp = colp + r0 * BN + 4 * cg;
+                    f32x4 csum = {0.f, 0.f, 0.f, 0.f};
+                    if (g.col_part && !(k == 0 && sl % P::SPU == 0)) csum = *reinterpret_cast<const f32x4*>(cpp);
+                    if (row < g.M && whole) {
+                        p += bn4;
+                        f32x4 xh, dp;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            xh[j] = fmaxf(p[j], 0.f);
+                            dd[j] = xh[j] - xv[j];
+                            dp[j] = (p[j] > 0.f) ? 2.f * dd[j] : 0.f;
+                        }
+                        if (g.xhat) *reinterpret_cast<f32x4*>(g.xhat + (int64_t)row * g.ldxhat + col) = xh;
+                        if (g.dP) *reinterpret_cast<f32x4*>(g.dP + (int64_t)row * g.lddp + col) = dp;
+                        if (g.dPp) {  // the same values, split once here for the dW / dX GEMMs that read them
+                            uint2 pk[3];
+                            x3_pack4_lean(f32x2{dp[0], dp[1]}, f32x2{dp[2], dp[3]}, pk);
+                            unsigned short* pp = g.dPp + (int64_t)row * g.lddpp + col;
+#pragma unroll
+                            for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<uint2*>(pp + pl * g.dp_pstride) = pk[pl];
+                        }
+                        csum += dp;
+                    } else if (row < g.M && edge) {
+                        p += bn4;
+                        const int xr = row % g.x_rows;
+                        for (int j = 0; j < g.N - col; ++j) {
+                            const float xhj = fmaxf(p[j], 0.f);
+                            const float d = xhj - g.x[(int64_t)xr * g.ldx + col + j];
+                            dd[j] = d;
+                            const float dpj = (p[j] > 0.f) ? 2.f * d : 0.f;
+                            if (g.xhat) g.xhat[(int64_t)row * g.ldxhat + col + j] = xhj;
+                            if (g.dP) g.dP[(int64_t)row * g.lddp + col + j] = dpj;
+                            csum[j] += dpj;
+                        }
+                    }
+                    *reinterpret_cast<f32x4*>(ps) = dd;  // (zeros outside the matrix: they change no sum)
+                    if (g.col_part) *reinterpret_cast<f32x4*>(cpp) = csum;
+                }
+                // the pass NSETS ahead, of this slice or the next (past the tile: rows nobody uses)
+                const int q = ti * P::KROWS + k + NSETS;
+                xs[k % NSETS] = q < NPASS ? x_request(sl, q / P::KROWS, q % P::KROWS)
+                                          : x_request(sl + 1, (q - NPASS) / P::KROWS, (q - NPASS) % P::KROWS);
+                __builtin_amdgcn_sched_barrier(0);  // (passes interleaved by the scheduler cost registers that are not there)
+            }
+        }
+        __syncthreads();
+        if (!STAGER) {
+            // se_part: multiplier thread 4 r + c forms chain c of row r (the stagers have the longer element work)
+            const int rl = tid >> 2, c = tid & 3;
+            const int row = bm * BM + sl * P::SLICE + rl;
+            float s = 0.f;
+#pragma unroll
+            for (int w = 0; w < WGN; ++w) {
+                float v = 0.f;
+#pragma unroll
+                for (int gq = 0; gq < P::WTN / 16; ++gq) {
+                    const int cl = w * P::WTN + 16 * gq + 4 * c;
+                    const int col = bn * BN + cl;
+                    const f32x4 dd = *reinterpret_cast<const f32x4*>(slice + rl * P::RS + cl);
+                    if (col < g.N && col + 3 >= g.N) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) v = __fmaf_rn(dd[j], dd[j], v);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) v = __fadd_rn(v, __fmul_rn(dd[j], dd[j]));
+                    }
+                }
+                v += __shfl_xor(v, 1, 64);
+                v += __shfl_xor(v, 2, 64);
+                s += v;
+            }
+            if (c == 0 && row < g.M) {
+                g.se_part[(int64_t)bn * g.M + row] = s;
+                if (bn == g.nt - 1)
+                    for (int tz = g.nt; tz < g.se_tiles; ++tz) g.se_part[(int64_t)tz * g.M + row] = 0.f;
+            }
+        } else {
+            if (g.col_part && unit_end && rt < BN) {
+                float t[P::BAND];
+#pragma unroll
+                for (int r = 0; r < P::BAND; ++r) t[r] = colp[r * BN + rt];
+#pragma unroll
+                for (int st = 1; st < P::BAND; st *= 2)
+#pragma unroll
+                    for (int r = 0; r < P::BAND; r += 2 * st) t[r] += t[r + st];
+                colw[(sl / P::SPU) * BN + rt] = t[0];
+                int cc = rt;  // (opaque again: the addresses of the final store are not to be carried through the slice loop)
+                asm volatile("" : "+v"(cc));
+                const int pc = bn * BN + cc;
+                if (sl == P::NSL - 1 && pc < g.N) {
+                    // col_part is [ceil(M / 128)][N]: one partial per 128-row half, its waves along M in order (this
+                    // thread wrote every colw entry it reads)
+#pragma unroll
+                    for (int hh = 0; hh < P::HALVES; ++hh) {
+                        float sum = 0.f;
+#pragma unroll
+                        for (int w = hh * P::WPH; w < (hh + 1) * P::WPH; ++w) sum += colw[w * BN + rt];
+                        const int prow = bm * P::HALVES + hh;
+                        if (prow * 128 < g.M) g.col_part[(int64_t)prow * g.N + pc] = sum;
+                    }
+                }
+            }
+        }
+        __syncthreads();  // the next dump -- or the stagers' next k-tile -- reuses the slice
+    }
+}
+
 template <int AFORM, int BFORM, int BM, int BN, int WGM, int WGN, int EPI, int ASRC = SRC_F32, int BSRC = SRC_F32>
 __global__ __launch_bounds__(512, 2) void gemm_x3w_kernel(const GemmArgs g) {
     static_assert(WGM * WGN == 4, "4 multiplier wavefronts");
@@ -1280,14 +1376,15 @@ __global__ __launch_bounds__(512, 2) void gemm_x3w_kernel(const GemmArgs g) {
     constexpr bool A_TR = A_PL && AFORM == FORM_RC, B_TR = B_PL && BFORM == FORM_RC;  // transposed-read images
     // 16x16x32 MFMAs: the same flops with a quarter of the accumulator registers per instruction -- the chip is
     // power-limited under this kernel and holds a ~10 % higher rate with them (profiles/r3_mfma_shape.txt, measured in
-    // this kernel: forward 103 -> 91 us).  The fused reconstruction epilogue keeps the 32x32 layout.
+    // this kernel: forward 103 -> 91 us).
     // Not for TN.  With fp32 operands that kernel is bound by its stagers (in-kernel split + transposing store) and the
     // short MFMAs take twice the issue slots of the SIMD the stager wave shares (160x256: 127 -> 137 us).  With planes
     // operands the 16-row fragments come out of the DMA'd k-major image by transposed reads whose four 16-lane groups
     // address the same 16 operand rows at k-rows 8 apart -- the same banks: 108 -> 128 us; trading the two 32-byte
     // halves of a slot in every other k-octet to separate them made it 320 us (profiles/r3_mfma16.txt).
     constexpr bool IS_TN = AFORM == FORM_RC && BFORM == FORM_RC;
-    constexpr bool MF16 = MMVAE_MFMA16 && MMVAE_XW_INTERLEAVE && !IS_TN;  // (both epilogues know the 16x16 layout)
+    // (the standard epilogue knows the 16x16 layout; the reconstruction epilogue over it is recon_lds_epilogue)
+    constexpr bool MF16 = MMVAE_MFMA16 && MMVAE_XW_INTERLEAVE && !IS_TN;
     static_assert(!MF16 || TK >= 2, "the in-place reload of the kept fragments needs two kept blocks");
     static_assert(2 * IMG + XW_SCRATCH <= 160 * 1024, "two images + scratch must fit the CU's LDS");
     __shared__ __attribute__((aligned(16))) char lds[2 * IMG + XW_SCRATCH];
@@ -1297,8 +1394,20 @@ __global__ __launch_bounds__(512, 2) void gemm_x3w_kernel(const GemmArgs g) {
     const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
     const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
     float* scratch = reinterpret_cast<float*>(lds + 2 * IMG);
-    // workgroup barriers an item's epilogue contains (the stagers take part in them)
-    const int epi_barriers = (EPI == EPI_RECON) ? 2 : (g.sq_part ? 2 : 0);
+    // The reconstruction epilogue over 16x16 accumulators runs from LDS on all eight waves (recon_lds_epilogue: both
+    // roles call it, its barriers included).  Otherwise: the workgroup barriers an item's epilogue contains, which the
+    // stagers take part in.
+    constexpr bool RECON_LDS = EPI == EPI_RECON && MF16;
+    if constexpr (RECON_LDS) static_assert(ReconLds<BM, BN, WGM, WGN>::BYTES <= IMG, "the epilogue's slice and partials live in ONE image");
+    const int epi_barriers = RECON_LDS ? 0 : (EPI == EPI_RECON) ? 2 : (g.sq_part ? 2 : 0);
+    // an item's epilogue in the stager role: `img` is the image the multipliers have just finished with
+    auto stager_epilogue = [&](int ebm, int ebn, int img) __attribute__((always_inline)) {
+        if constexpr (RECON_LDS) {
+            recon_lds_epilogue<BM, BN, WGM, WGN, true>(g, ebm, ebn, lds + img * IMG, [](int) {});
+        } else {
+            for (int e = 0; e < epi_barriers; ++e) __syncthreads();
+        }
+    };
 
     if (tid >= NT) {
         // ------------------------------------------------------------------------------------------------ stagers
@@ -1480,8 +1589,11 @@ __global__ __launch_bounds__(512, 2) void gemm_x3w_kernel(const GemmArgs g) {
 #if MMVAE_X3_STAMPS
             sst[3] += 1;
 #endif
-            if (br_c.template advance<NFAST>(g, nwg))
-                for (int e = 0; e < epi_barriers; ++e) __syncthreads();
+            // (element s was multiplied out of image 0 here, out of image 1 below)
+            {
+                const int ebm = br_c.bm, ebn = br_c.bn;
+                if (br_c.template advance<NFAST>(g, nwg)) stager_epilogue(ebm, ebn, 0);
+            }
             if (!br_c.valid(g)) break;
             step(S0{}, 0);
             XW_SSTAMP(0)
@@ -1490,8 +1602,10 @@ __global__ __launch_bounds__(512, 2) void gemm_x3w_kernel(const GemmArgs g) {
 #if MMVAE_X3_STAMPS
             sst[3] += 1;
 #endif
-            if (br_c.template advance<NFAST>(g, nwg))
-                for (int e = 0; e < epi_barriers; ++e) __syncthreads();
+            {
+                const int ebm = br_c.bm, ebn = br_c.bn;
+                if (br_c.template advance<NFAST>(g, nwg)) stager_epilogue(ebm, ebn, 1);
+            }
             if (!br_c.valid(g)) break;
         }
 #if MMVAE_X3_STAMPS
@@ -1874,8 +1988,47 @@ __global__ __launch_bounds__(512, 2) void gemm_x3w_kernel(const GemmArgs g) {
 #if MMVAE_X3_STAMPS
         if (tid == 0 && bid < 4096) g_x3_trace[bid * 4 + 2] = wall_clock64();
 #endif
-        gemm_epilogue<BM, BN, WGM, WGN, EPI, TM, TN, MF16>(acc, g, bm, bn, z, scratch);
-        if (EPI == EPI_RECON) __syncthreads();
+        if constexpr (RECON_LDS) {
+            // slice sl = tile rows 64 sl .. 64 sl + 63 = row blocks i = 2 h, 2 h + 1 of the waves with wm = sl / SPW
+            // (h = sl % SPW).  Register 4 gq + j of a block: row 16 (gq >> 1) + 4 (lane >> 4) + j, column 16 (gq & 1) +
+            // (lane & 15).  The accumulator indices are compile-time in every branch: sl only selects the branch.
+            constexpr int SPW = WTM / 64;
+            static_assert(WTM % 64 == 0 && TM == 2 * SPW, "whole 64-row slices per multiplier wave");
+            char* buf = lds + ((s - 1) & 1) * IMG;  // the image of the k-tile just finished
+            int elane = lane;  // (opaque: the store addresses are derived behind the main loop, see recon_lds_epilogue)
+            asm volatile("" : "+v"(elane));
+            float* dst = reinterpret_cast<float*>(buf) + (4 * (elane >> 4)) * ReconLds<BM, BN, WGM, WGN>::RS + wn * WTN + (elane & 15);
+            recon_lds_epilogue<BM, BN, WGM, WGN, false>(g, bm, bn, buf, [&](int sl) __attribute__((always_inline)) {
+                if (wm != sl / SPW) return;
+                // (a wave with two slices picks the VALUES by sl, element by element: two branches over acc[0..1] and
+                // acc[2..3] are merged by the compiler into one over a run-time index, which puts acc into scratch)
+                const bool second = SPW == 2 && (sl % SPW) != 0;
+#pragma unroll
+                for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+                    for (int n = 0; n < TN; ++n)
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) {
+                            const float lo = acc[ii][n][e], hi = acc[SPW == 2 ? 2 + ii : ii][n][e];
+                            dst[(32 * ii + 16 * (e >> 3) + (e & 3)) * ReconLds<BM, BN, WGM, WGN>::RS + 32 * n + 16 * ((e >> 2) & 1)] =
+                                second ? hi : lo;
+                        }
+            });
+            // The next item's first fragments were read under the last MFMAs (the main loop reads one k-tile ahead).  Read
+            // again here they are not live across the epilogue, which would not fit beside them and the accumulators.
+            if (c.valid(g)) {
+                const char* cur = lds + (s & 1) * IMG;
+#pragma unroll
+                for (int p = 0; p < 3; ++p) {
+#pragma unroll
+                    for (int sb = 0; sb < 2 * TK; ++sb) fk[sb & 1][p][sb >> 1] = frag16K(cur, p, sb);
+                    fs[0][p] = frag16S(cur, p, 0);
+                }
+            }
+        } else {
+            gemm_epilogue<BM, BN, WGM, WGN, EPI, TM, TN, MF16>(acc, g, bm, bn, z, scratch);
+            if (EPI == EPI_RECON) __syncthreads();
+        }
 #if MMVAE_X3_STAMPS
         tq_ = clock64();
 #endif
