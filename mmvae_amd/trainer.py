@@ -421,6 +421,23 @@ class Trainer:
         return silhouette_widths(z, metadata, **kw)
 
     @torch.no_grad()
+    def cluster_metrics(self, model, batches: Iterable, **kw):
+        """`mmvae_amd.clustering.cluster_metrics` of the latent embeddings: z and the metadata gathered exactly as
+        `silhouette_widths` gathers them, then per label column a k-means of all cells and its NMI and ARI against the
+        labels.  `kw`: label_keys, n_clusters, seed, n_init, max_iter."""
+        import pandas as pd
+
+        from .clustering import cluster_metrics
+        from .constants import REGISTRY_KEYS as RK
+
+        outs = [p[RK.Z] for p in self.predict(model, batches)]
+        if not outs:
+            raise ValueError("Trainer.cluster_metrics: no batches")
+        z = torch.cat([o[0] for o in outs], 0)
+        metadata = pd.concat([o[1] for o in outs], ignore_index=True)
+        return cluster_metrics(z, metadata, **kw)
+
+    @torch.no_grad()
     def correlations(self, model, groups: Iterable, decimals: Optional[int] = 3):
         """The table of get_correlations (runners/run_correlations.py:95-145) as a pandas.DataFrame, one row per group of
         `groups` = (group_id, batch_a, batch_b) with the two batches of different experts
