@@ -438,6 +438,24 @@ class Trainer:
         return cluster_metrics(z, metadata, **kw)
 
     @torch.no_grad()
+    def graph_metrics(self, model, batches: Iterable, **kw):
+        """`mmvae_amd.graph_metrics.graph_metrics` of the latent embeddings: z and the metadata gathered exactly as
+        `integration_metrics` gathers them, then the graph connectivity of every label column and kBET of the batch
+        column (whole graph and per label class) on the exact kNN graph of z.  `kw`: batch_key, label_keys, n_neighbors,
+        alpha."""
+        import pandas as pd
+
+        from .constants import REGISTRY_KEYS as RK
+        from .graph_metrics import graph_metrics
+
+        outs = [p[RK.Z] for p in self.predict(model, batches)]
+        if not outs:
+            raise ValueError("Trainer.graph_metrics: no batches")
+        z = torch.cat([o[0] for o in outs], 0)
+        metadata = pd.concat([o[1] for o in outs], ignore_index=True)
+        return graph_metrics(z, metadata, **kw)
+
+    @torch.no_grad()
     def correlations(self, model, groups: Iterable, decimals: Optional[int] = 3):
         """The table of get_correlations (runners/run_correlations.py:95-145) as a pandas.DataFrame, one row per group of
         `groups` = (group_id, batch_a, batch_b) with the two batches of different experts
