@@ -186,6 +186,8 @@ size_t mmvae_sizeof_split_job(void);
  * Forward:   z = bias + sum_s in[s]            (in: [S, B, ld] slabs; S = 1 for a plain GEMM output)
  *            BN (has_bn): training: batch mean / biased var over B, running stats updated with unbiased var;
  *                         eval: running stats.            y = gamma * (z - mean) * invstd + beta
+ *                         A batch of one row in training (torch refuses it) is accepted: save_mean = z, save_invstd =
+ *                         1 / sqrt(eps), y = beta, and running_var moves towards 0 (the variance 0 is not rescaled).
  *            a = relu ? max(y, 0) : y                      (the tensor the reference collects as "hidden" after "af")
  *            d = mask ? a * mask * (1 / (1 - p)) : a        (mask: u8 0/1 keep mask, parity mode or Philox-filled)
  * Outputs: z_out (needed by BN backward; may be NULL when !has_bn), a_out (may be NULL when no dropout and
