@@ -456,6 +456,23 @@ class Trainer:
         return graph_metrics(z, metadata, **kw)
 
     @torch.no_grad()
+    def pc_regression(self, model, batches: Iterable, **kw):
+        """`mmvae_amd.pca.pc_regression` of the latent embeddings: z and the metadata gathered exactly as `graph_metrics`
+        gathers them, then the PCA of z and the principal-component regression of every covariate column (categorical
+        or numeric) on it.  `kw`: covariates, n_comps."""
+        import pandas as pd
+
+        from .constants import REGISTRY_KEYS as RK
+        from .pca import pc_regression
+
+        outs = [p[RK.Z] for p in self.predict(model, batches)]
+        if not outs:
+            raise ValueError("Trainer.pc_regression: no batches")
+        z = torch.cat([o[0] for o in outs], 0)
+        metadata = pd.concat([o[1] for o in outs], ignore_index=True)
+        return pc_regression(z, metadata, **kw)
+
+    @torch.no_grad()
     def correlations(self, model, groups: Iterable, decimals: Optional[int] = 3):
         """The table of get_correlations (runners/run_correlations.py:95-145) as a pandas.DataFrame, one row per group of
         `groups` = (group_id, batch_a, batch_b) with the two batches of different experts
